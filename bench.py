@@ -84,7 +84,13 @@ def parse():
                          "eight rank shares of configs[3] time-multiplexed on this GPU + the fold (tests/big_c4.py in a subprocess "
                          "with a timeout; never able to lose the main line).  auto: when the host has the memory and --no-extras is not set")
     ap.add_argument("--whole-genome-timeout", type=float, default=900.0)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the rows of the last timed step's PREFIX.mums to DIR as .npy files "
+                         "(lengths, offsets, strands and the row numbers of a fixed sample of at most DUMP_BYTES in all)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def pick_workdir(a, need_bytes):
@@ -98,6 +104,41 @@ def pick_workdir(a, need_bytes):
         except OSError:
             pass
     return tempfile.mkdtemp(prefix="mumemto_bench_"), "tmp"
+
+
+DUMP_BYTES = 64_000_000   # --dump-outputs: the .npy files together stay below this
+DUMP_SEED = 12345         # the rows sampled when the whole table does not fit
+
+
+def dump_mums(path, out_dir):
+    """The rows of a PREFIX.mums file -- what a caller of the timed path receives -- as float64 / float32 .npy files: row
+    numbers, lengths, offsets (-1 = absent) and strands (1 = '+') of every row, or of a fixed seeded sample of the rows
+    when the table is larger than DUMP_BYTES.  Returns what was written."""
+    os.makedirs(out_dir, exist_ok=True)
+    with open(path, "rb") as f:
+        lines = f.read().split(b"\n")
+    if lines and not lines[-1]:
+        lines.pop()
+    n = len(lines)
+    n_docs = lines[0].split(b"\t")[1].count(b",") + 1 if n else 0
+    per_row = 8 + 8 + n_docs * (8 + 4)                       # row number, length, offsets (f64), strands (f32)
+    keep = min(n, (DUMP_BYTES - 4 * 4096) // per_row)        # (room for the .npy headers)
+    rows = np.arange(n) if keep == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False))
+    lengths = np.empty(keep, np.float64)
+    offsets = np.empty((keep, n_docs), np.float64)
+    strands = np.empty((keep, n_docs), np.float32)
+    for i, r in enumerate(rows.tolist()):
+        length, offs, sts = lines[r].split(b"\t")[:3]
+        lengths[i] = int(length)
+        offsets[i] = [int(x) if x else -1 for x in offs.split(b",")]
+        strands[i] = [x == b"+" for x in sts.split(b",")]
+    del lines
+    arrays = {"mums_row": rows.astype(np.float64), "mums_length": lengths, "mums_offsets": offsets, "mums_strand": strands}
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return {"dir": out_dir, "file": os.path.basename(path), "rows": n, "rows_written": int(keep), "documents": n_docs,
+            "sample_seed": None if keep == n else DUMP_SEED,
+            "bytes": int(sum(arr.nbytes for arr in arrays.values())), "arrays": sorted(arrays)}
 
 
 def cpu_baseline(sample):
@@ -250,6 +291,7 @@ def main():
     #      "wall-clock from process start to last byte of PREFIX.mums closed".
     exe = os.path.join(ROOT, "mumemto_amd", "bin", "mumemto_exec")
     fresh = None
+    dumped = None
     if rank == 0 and world == 1 and not a.in_process and not a.realistic and os.path.exists(exe):
         stats = os.path.join(workdir, "cli_stats.json")
         runs = []
@@ -273,6 +315,8 @@ def main():
                 rec["stderr_tail"] = r.stderr.decode(errors="replace")[-400:]
             runs.append(rec)
         timed = [x for x in runs if x["timed"]]
+        if a.dump_outputs and timed and all(x["rc"] == 0 for x in timed):
+            dumped = dump_mums(os.path.join(workdir, "cli.mums"), a.dump_outputs)
         # the same job with NO pause between the processes: what a process that starts right behind another one pays for the
         # memory its predecessor gave back (the driver scrubs it; the figure the pause keeps out of `value`)
         b2b = []
@@ -390,6 +434,8 @@ def main():
         stage_acc += np.array(ms)
     fence()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and fresh is None and rank == 0:
+        dumped = dump_mums(out_prefix + ".mums", a.dump_outputs)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -483,6 +529,7 @@ def main():
                            "frac": sum(col) * n_text / max(float(stage_acc[6]) / in_steps, 1e-9) / 1e6 / HBM_PEAK_GBS},
         "device_memory": eng.device_memory(),
         "generate_s": t_gen,
+        "dump_outputs": dumped,
     }
     # HBM bytes the scan kernel really moved, from the PMC passes under profiles/ (separate rocprofv3 runs of this
     # command line; FETCH_SIZE doubled per the gfx950 note of MI355X_MICROARCH.md), valid for the default workload only

@@ -299,10 +299,11 @@ def _realistic_to_file(args):
         return len(s)
 
 
-def collection_realistic(n_haps, length, divergence, seed, which=None, procs=1, **kw):
+def collection_realistic(n_haps, length, divergence, seed, which=None, procs=1, start="fork", **kw):
     """The haplotypes `haplotypes_realistic` yields for `which` as ONE flat uint8 array + their (unequal) lengths.  procs > 1:
     a haplotype per worker process (each makes the ancestor again: ~7 bytes of host memory per base and worker at its peak),
-    handed over through files in /dev/shm."""
+    handed over through files in /dev/shm.  start: how the workers are started (multiprocessing start method; "spawn" from a
+    process that holds a GPU, whose forks would hold it too)."""
     import os
     which = list(range(n_haps) if which is None else which)
     shm = "/dev/shm"
@@ -313,7 +314,7 @@ def collection_realistic(n_haps, length, divergence, seed, which=None, procs=1, 
     tag = "mmt_real_%d_%d_" % (os.getpid(), seed)
     paths = [os.path.join(shm, tag + "%03d.npy" % h) for h in which]
     try:
-        with mp.get_context("fork").Pool(min(procs, len(which))) as pool:
+        with mp.get_context(start).Pool(min(procs, len(which))) as pool:
             lens = pool.map(_realistic_to_file, [(n_haps, length, divergence, seed, h, p, kw) for h, p in zip(which, paths)], chunksize=1)
         bases = np.empty(int(sum(lens)), np.uint8)
         at = 0

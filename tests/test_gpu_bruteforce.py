@@ -7,7 +7,8 @@ file: reverse-complement palindromes at document ends, tandem duplications, runs
 documents, min_len 4 - 20 -- go through libmumemto's C ABI on the GPU and their PREFIX.mums / .mems bytes must equal the
 checker's: two independent checkers bracket the GPU path itself.  In the strict mode every fourth case also compares the
 thresholds of A7 with their definition.  The checker is slow (seconds per case): the expected bytes are computed on the
-host's cores in parallel while the GPU runs."""
+host's cores in parallel while the GPU runs, by fresh worker processes (spawned, not forked: a fork of this process would
+hold its handle on the GPU)."""
 import multiprocessing as mp
 import os
 
@@ -42,7 +43,7 @@ def test_hip_path_equals_the_definition_checker(producer):
         os.environ["MMT_GUIDED_BATCH"] = "400"
     bad, rows = [], 0
     try:
-        with mp.get_context("fork").Pool(workers) as pool:
+        with mp.get_context("spawn").Pool(workers) as pool:
             for mode, seed, want, th in pool.imap_unordered(_expected, jobs, chunksize=4):
                 docs, revcomp, min_len, nd, f, F = make_case(seed, mode)
                 eng.set_docs(docs)

@@ -8,7 +8,11 @@ size differs from the message FAILS), and everything above the transport is the 
 share with merge metadata, `mmt_dist_merge` (rank 0 folds) and `mmt_dist_merge_ranges` (every rank folds its slice of the
 anchor: all-to-all of row and threshold slices, pieces to rank 0) must give the bytes of the oracle's direct run on the
 union; `mmt_dist_gather_text` must give the single-GPU bytes of the sharded modes; `mumemto_exec --gpus N` runs the same
-through the command line."""
+through the command line.
+
+A GPU admits only a few processes at once: at most MAX_RANK_PROCS worker processes are started, and a world larger than
+that puts several ranks in one process, each on a thread of its own with its own engine and communicator (the double keeps
+its group state per thread; the fold keeps its scratch per device and thread)."""
 import os
 import subprocess
 import sys
@@ -33,54 +37,79 @@ def fake_lib():
 
 
 _WORKER = r"""
-import os, sys, time
+import os, sys, threading, time, traceback
 root = %(root)r
 sys.path[:0] = [root, os.path.join(root, "oracle"), os.path.join(root, "tests")]
 import numpy as np
 import mumemto_amd
 from mumemto_amd import synth
 from mumemto_amd import dist as mdist
-rank, world, idfile, outdir, what = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], sys.argv[4], sys.argv[5]
+ranks, world, idfile, outdir, what = [int(r) for r in sys.argv[1].split(",")], int(sys.argv[2]), sys.argv[3], sys.argv[4], sys.argv[5]
 docs = synth.pangenome(%(haps)d, %(length)d, 0.01, seed=%(seed)d, inversion=(2, 2000, 5000), indel_rate=0.0005)
-eng = mumemto_amd.Engine(0)
-if rank == 0:
-    uid = mumemto_amd.Comm.unique_id()
-    with open(idfile + ".tmp", "wb") as f: f.write(uid)
-    os.rename(idfile + ".tmp", idfile)
-else:
-    t0 = time.time()
-    while not os.path.exists(idfile):
-        assert time.time() - t0 < 120
-        time.sleep(0.01)
-    uid = open(idfile, "rb").read()
-comm = mumemto_amd.Comm(eng, rank, world, uid)
-if what in ("rank0", "ranges", "auto"):
-    mine = mdist.partition_docs(len(docs), world)[rank]
-    if %(max_text)d:
-        os.environ["MMT_MAX_TEXT"] = str(%(max_text)d)        # the share runs as anchor partitions inside the rank
-    eng.run_partitioned([docs[i] for i in mine], merge_metadata=True)
-    if what == "auto":
-        m = comm.merge()
+def run_rank(rank):
+    eng = mumemto_amd.Engine(0)
+    if rank == 0:
+        uid = mumemto_amd.Comm.unique_id()
+        with open(idfile + ".tmp", "wb") as f: f.write(uid)
+        os.rename(idfile + ".tmp", idfile)
     else:
-        m = comm.merge(by_ranges=(what == "ranges"))
-    assert (m is not None) == (rank == 0)
-    if rank == 0:
-        open(os.path.join(outdir, "merged.mums"), "wb").write(m["text"])
+        t0 = time.time()
+        while not os.path.exists(idfile):
+            assert time.time() - t0 < 120
+            time.sleep(0.01)
+        uid = open(idfile, "rb").read()
+    comm = mumemto_amd.Comm(eng, rank, world, uid)
+    if what in ("rank0", "ranges", "auto"):
+        mine = mdist.partition_docs(len(docs), world)[rank]
+        if %(max_text)d:
+            os.environ["MMT_MAX_TEXT"] = str(%(max_text)d)    # the share runs as anchor partitions inside the rank
+        eng.run_partitioned([docs[i] for i in mine], merge_metadata=True)
+        if what == "auto":
+            m = comm.merge()
+        else:
+            m = comm.merge(by_ranges=(what == "ranges"))
+        assert (m is not None) == (rank == 0)
+        if rank == 0:
+            open(os.path.join(outdir, "merged.mums"), "wb").write(m["text"])
+    else:
+        kw = dict(num_distinct=%(haps)d - 1, max_doc_freq=3, max_total_freq=3 * %(haps)d)
+        if what == "sharded_sort":
+            eng.set_producer("guided")
+            os.environ["MMT_GUIDED_BATCH"] = "4000"
+        eng.set_docs(docs)
+        eng.set_scan_shard(rank, world)
+        eng.run(**kw)
+        text = comm.gather_text()
+        assert (len(text) > 0) == (rank == 0)
+        if rank == 0:
+            open(os.path.join(outdir, "gathered.mems"), "wb").write(text)
+    comm.close(); eng.close()
+    print("RANK_OK", rank, flush=True)
+
+def on_thread(rank):
+    try:
+        run_rank(rank)
+    except BaseException:
+        # the other ranks would wait for this one in a collective: the process ends here, as a failed rank process would
+        sys.stderr.write("rank %%d:\n%%s" %% (rank, traceback.format_exc()))
+        sys.stderr.flush()
+        os._exit(1)
+
+if len(ranks) == 1:
+    run_rank(ranks[0])
 else:
-    kw = dict(num_distinct=%(haps)d - 1, max_doc_freq=3, max_total_freq=3 * %(haps)d)
-    if what == "sharded_sort":
-        eng.set_producer("guided")
-        os.environ["MMT_GUIDED_BATCH"] = "4000"
-    eng.set_docs(docs)
-    eng.set_scan_shard(rank, world)
-    eng.run(**kw)
-    text = comm.gather_text()
-    assert (len(text) > 0) == (rank == 0)
-    if rank == 0:
-        open(os.path.join(outdir, "gathered.mems"), "wb").write(text)
-comm.close(); eng.close()
-print("RANK_OK", rank)
+    threads = [threading.Thread(target=on_thread, args=(r,)) for r in ranks]
+    for t in threads: t.start()
+    for t in threads: t.join()
 """
+
+# processes with GPU 0 open at once, the test process aside; ranks beyond that share processes
+MAX_RANK_PROCS = 4
+
+
+def rank_groups(world):
+    """The ranks of each worker process: one rank a process up to MAX_RANK_PROCS ranks, then round robin."""
+    return [list(range(p, world, MAX_RANK_PROCS)) for p in range(min(world, MAX_RANK_PROCS))]
 
 
 def run_ranks(world, what, haps=9, length=30000, seed=71, max_text=0, env_extra=None):
@@ -91,8 +120,9 @@ def run_ranks(world, what, haps=9, length=30000, seed=71, max_text=0, env_extra=
             f.write(_WORKER % dict(root=ROOT, haps=haps, length=length, seed=seed, max_text=max_text))
         env = dict(os.environ, MUMEMTO_RCCL_LIB=lib, MUMEMTO_NO_TORCH="1")
         env.update(env_extra or {})
-        procs = [subprocess.Popen([sys.executable, script, str(r), str(world), os.path.join(d, "id"), d, what], env=env,
-                                  stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for r in range(world)]
+        groups = rank_groups(world)
+        procs = [subprocess.Popen([sys.executable, script, ",".join(map(str, g)), str(world), os.path.join(d, "id"), d, what],
+                                  env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for g in groups]
         outs = []
         for p in procs:
             try:
@@ -101,8 +131,9 @@ def run_ranks(world, what, haps=9, length=30000, seed=71, max_text=0, env_extra=
                 for q in procs:
                     q.kill()
                 raise
-        for r, (p, (so, se)) in enumerate(zip(procs, outs)):
-            assert p.returncode == 0 and "RANK_OK" in so, "rank %d:\n%s\n%s" % (r, so[-2000:], se[-4000:])
+        for g, p, (so, se) in zip(groups, procs, outs):
+            assert p.returncode == 0 and all("RANK_OK %d\n" % r in so for r in g), \
+                "ranks %s:\n%s\n%s" % (g, so[-2000:], se[-4000:])
         name = "merged.mums" if what in ("rank0", "ranges", "auto") else "gathered.mems"
         with open(os.path.join(d, name), "rb") as f:
             return f.read()

@@ -144,8 +144,9 @@ def test_giant_phrases_of_the_bucket_wise_producer_equal_the_oracle(depth, haps,
 
 
 def _flat(haps, length, div, seed):
-    # (a haplotype per worker process: indels and inversions are minutes of numpy at whole-genome size)
-    return synth.collection_realistic(haps, length, div, seed, procs=2 if length > 1_000_000_000 else 8)
+    # (a haplotype per worker process: indels and inversions are minutes of numpy at whole-genome size; spawned, since a fork of
+    # this process would hold its handle on the GPU)
+    return synth.collection_realistic(haps, length, div, seed, procs=2 if length > 1_000_000_000 else 8, start="spawn")
 
 
 def test_realistic_collection_of_c3_size():

@@ -226,6 +226,6 @@ def test_fast_generators_yield_the_haplotypes_numpy_would():
     out = np.empty_like(big)
     synth.copy_threaded(out, big, threads=3, piece=1 << 20)
     assert np.array_equal(out, big)
-    cb, cl = synth.collection_realistic(5, 300_000, 0.001, 3, which=[1, 4], procs=2)
+    cb, cl = synth.collection_realistic(5, 300_000, 0.001, 3, which=[1, 4], procs=2, start="spawn")
     seqs = [s for _, s in synth.haplotypes_realistic(5, 300_000, 0.001, 3, which=[1, 4])]
     assert np.array_equal(cb, np.concatenate(seqs)) and list(cl) == [len(s) for s in seqs]

@@ -143,7 +143,7 @@ def test_oracle_scan_equals_the_definition_checker_in_volume(mode):
     workers = max(1, min(16, len(os.sched_getaffinity(0))))
     seeds = list(range(CASES))
     chunks = [(mode, seeds[i::workers * 4]) for i in range(workers * 4)]
-    with mp.get_context("fork").Pool(workers) as pool:
+    with mp.get_context("spawn").Pool(workers) as pool:      # (not forked: the suite's process may hold the GPU by now)
         res = pool.map(run_chunk, chunks)
     bad = [b for r in res for b in r[0]]
     rows = sum(r[1] for r in res)
