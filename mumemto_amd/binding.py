@@ -360,6 +360,18 @@ class Engine:
         _check(self.L.mmt_engine_set_stream_host(self.h, _p(sa), _p(lcp), _p(bwt), C.c_uint64(len(sa)), _p(lens), len(lens),
                                                  int(use_revcomp)))
 
+    def set_stream40(self, sa, lcp, bwt, doc_len, use_revcomp=True):
+        """set_stream for suffix-array entries of up to 40 bits (sa: int64), over a text of any length."""
+        sa = np.ascontiguousarray(sa, np.uint64)
+        if len(sa) and int(sa.max()) >> 40:
+            raise ValueError("suffix-array entry beyond 40 bits")
+        lo = np.ascontiguousarray(sa & 0xffffffff, np.uint32)
+        hi = np.ascontiguousarray(sa >> 32, np.uint8)
+        lcp = np.ascontiguousarray(lcp, np.uint32)
+        bwt = np.ascontiguousarray(bwt, np.uint8); lens = np.ascontiguousarray(doc_len, np.uint64)
+        _check(self.L.mmt_engine_set_stream_host40(self.h, _p(lo), _p(hi), _p(lcp), _p(bwt), C.c_uint64(len(lo)), _p(lens),
+                                                   len(lens), int(use_revcomp)))
+
     def run(self, min_match_len=20, num_distinct=0, max_doc_freq=1, max_total_freq=0, use_revcomp=True,
             merge_metadata=False):
         p = Params(min_match_len, num_distinct, max_doc_freq, max_total_freq, int(use_revcomp), int(merge_metadata))

@@ -81,20 +81,24 @@ static std::vector<uint8_t> read_whole_file(const std::string& path, const char*
 }
 // -a PREFIX (src/pfp_mum.cpp:97-111, include/read_arrays.hpp:86-122): 40-bit little-endian SA / LCP, one BWT byte
 // per entry.  The reference feeds the first |T| entries of the |T|+1 the writer produced to the match finder, i.e.
-// the sentinel entry and all real suffixes but the last; the engine takes exactly those real suffixes.
+// the sentinel entry and all real suffixes but the last; the engine takes exactly those real suffixes.  Files that
+// hold a prefix of the stream (E < |T| entries, the same E in all three) are scanned entry by entry like the library's
+// set_stream_host40 does: the real suffixes among those E entries.
 static void load_stream_files(const std::string& prefix, uint64_t text_chars, std::vector<uint32_t>& sa,
                               std::vector<uint8_t>& sa_hi, std::vector<uint32_t>& lcp, std::vector<uint8_t>& bwt) {
     const std::vector<uint8_t> fsa = read_whole_file(prefix + ".sa", "SA"), flcp = read_whole_file(prefix + ".lcp", "LCP"),
                                fbwt = read_whole_file(prefix + ".bwt", "BWT");
-    if (fsa.size() < text_chars * 5 || flcp.size() < text_chars * 5 || fbwt.size() < text_chars)
+    const uint64_t in_files = fbwt.size();
+    const bool prefix_only = in_files < text_chars && fsa.size() == in_files * 5 && flcp.size() == in_files * 5 && in_files;
+    if (!prefix_only && (fsa.size() < text_chars * 5 || flcp.size() < text_chars * 5 || fbwt.size() < text_chars))
         throw CliError{"the arrays under " + prefix + " hold fewer than the " + std::to_string(text_chars) +
-                       " entries the lengths file announces", 1};
+                       " entries the lengths file announces, and are not a prefix of the stream (equal entry counts)", 1};
     auto get40 = [](const std::vector<uint8_t>& b, uint64_t j) {
         uint64_t v = 0;
         for (int k = 4; k >= 0; k--) v = (v << 8) | b[j * 5 + k];
         return v;
     };
-    const uint64_t entries = text_chars ? text_chars - 1 : 0;      // stream entries 1 .. |T|-1
+    const uint64_t entries = prefix_only ? in_files - 1 : text_chars ? text_chars - 1 : 0;   // stream entries 1 .. |T|-1
     sa.resize(entries); lcp.resize(entries); bwt.resize(entries);
     const bool wide = text_chars >= NARROW_LIMIT;          // positions need the high byte (wide.hpp)
     if (wide) sa_hi.resize(entries);
@@ -847,7 +851,9 @@ int main(int argc, char** argv) {
         const uint64_t max_text = eng.auto_max_text();
         const bool strict_mode = mum_mode && (o.num_distinct_docs == 0 || (size_t)o.num_distinct_docs == doc_len.size());
         // modes without a partition merge are tried as one run whatever the estimate says, like the library does
-        bool partitioned = text_chars > max_text && doc_len.size() >= 3 && (strict_mode || explicit_limit);
+        // (-a: what the device holds is the stream in the files, which may be a prefix of a stream over a longer text)
+        const uint64_t device_chars = o.arrays_in_flag ? (uint64_t)ck_sa.size() + 1 : text_chars;
+        bool partitioned = device_chars > max_text && doc_len.size() >= 3 && (strict_mode || explicit_limit);
         if (checkpoint && partitioned) throw CliError{"-p / -a are not available for inputs larger than one suffix array", 1};
         if (checkpoint && (o.keep_temp || o.arrays_out))
             throw CliError{"-K and -A write what -p / -a read: run them without a checkpoint", 1};

@@ -10,8 +10,8 @@
  * behaviour it restates.  Parity pin status (see DESIGN.md "Oracle"):
  *   - scan/writers: pinned by the known-answer vectors of SURVEY.md 8(c)
  *     (tests/golden/toy_vectors.json) and by a brute-force definition checker
- *     (tests/bruteforce.py); the reference's mem_finder.hpp cannot be built
- *     here (needs sdsl + gsacak, un-vendored).
+ *     (tests/bruteforce.py), and byte for byte against the reference's own
+ *     mem_finder.hpp (oracle/_ref/mem_finder_ref, tests/test_refscan_host.py).
  *   - anchor merge: pinned against the real reference build
  *     oracle/_ref/anchor_merge (src/merge_candidates.cpp compiles stand-alone).
  *   - PFP parse/dictionary: pinned against oracle/_ref/newscan_ref
