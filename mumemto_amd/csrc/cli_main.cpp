@@ -29,6 +29,7 @@
 #include "fasta.hpp"
 #include "merge.hpp"
 #include "options.hpp"
+#include "out_file.hpp"
 
 namespace fs = std::filesystem;
 using namespace mmt;
@@ -215,24 +216,21 @@ static int launch_ranks(int argc, char** argv, const BuildOptions& o) {
     for (const char* ext : {".mums", ".mems"}) {
         const std::string first = o.output_prefix + ".rank0" + ext;
         if (rc || !fs::exists(first)) continue;
-        // joined under a temporary name and renamed when every piece is in: a short write or a kill half way leaves no
-        // plausible but truncated PREFIX.mems; the pieces go only after the joined file is complete
-        const std::string final_name = o.output_prefix + ext, tmp = final_name + ".tmp";
-        {
-            std::ofstream all(tmp, std::ios::binary | std::ios::trunc);
+        // joined under a temporary name and renamed when every piece is in (OutFile); the pieces go only after that
+        try {
+            OutFile all;
+            all.open(o.output_prefix + ext);
             std::vector<char> buf(64u << 20);
-            for (int r = 0; r < o.gpus && !rc; r++) {
+            for (int r = 0; r < o.gpus; r++) {
                 const std::string piece = o.output_prefix + ".rank" + std::to_string(r) + ext;
                 std::ifstream in(piece, std::ios::binary);
-                if (!in) { log_line("build_main", "the piece of rank " + std::to_string(r) + " is missing: " + piece); rc = 1; break; }
-                while (in && all) { in.read(buf.data(), (std::streamsize)buf.size()); all.write(buf.data(), in.gcount()); }
-                if (!all || in.bad()) { log_line("build_main", "could not write " + tmp + " (piece of rank " + std::to_string(r) + ")"); rc = 1; }
+                if (!in) throw std::runtime_error("the piece of rank " + std::to_string(r) + " is missing: " + piece);
+                while (in.read(buf.data(), (std::streamsize)buf.size()), in.gcount() > 0)
+                    if (!all.write_all(buf.data(), (size_t)in.gcount())) throw std::runtime_error(all.error());
+                if (in.bad()) throw std::runtime_error("could not read " + piece);
             }
-            all.close();
-            if (!rc && !all) { log_line("build_main", "could not write " + tmp); rc = 1; }
-        }
-        if (!rc && std::rename(tmp.c_str(), final_name.c_str()) != 0) { log_line("build_main", "could not rename " + tmp); rc = 1; }
-        if (rc) { std::remove(tmp.c_str()); continue; }
+            all.commit();
+        } catch (const std::exception& ex) { log_line("build_main", ex.what()); rc = 1; continue; }
         for (int r = 0; r < o.gpus; r++) std::remove((o.output_prefix + ".rank" + std::to_string(r) + ext).c_str());
     }
     return rc;

@@ -1,11 +1,8 @@
 // engine.cpp -- orchestration of the hot path on one GPU (no kernels here).
 #include "engine.hpp"
 
-#include <sys/stat.h>
 #include "fasta.hpp"
 
-#include <fcntl.h>
-#include <unistd.h>
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
@@ -18,7 +15,14 @@ namespace mmt {
 
 static int bit_width_u64(uint64_t v) { int b = 0; while (v) { b++; v >>= 1; } return b; }
 
-Engine::Engine(int device, hipStream_t stream) : device_(device), stream_(stream) {
+// (64 MB: page-locking costs 0.19 s per GB when a block is made and 0.13 s per GB when the process ends -- four blocks of
+// 256 MB were a quarter of a second of the bench workload's 2.2 s from process start to exit)
+static size_t sink_block_bytes() {
+    const char* mb = std::getenv("MMT_SINK_BLOCK_MB");
+    return (size_t)(mb ? std::max(1, std::atoi(mb)) : 64) << 20;
+}
+
+Engine::Engine(int device, hipStream_t stream) : device_(device), stream_(stream), sink_writer_(sink_block_bytes(), 4) {
     lean_ = std::getenv("MUMEMTO_LEAN") != nullptr;      // tests: stage scratch is released between the stages
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
@@ -831,11 +835,66 @@ void Engine::order_rows(const k::Row* rows_abs, uint32_t cnt) {
     }
 }
 
+// the place of the PREFIX.mums / .mems bytes is asked for when their number is known; one synchronisation of the stream
+Engine::RowsFormat Engine::format_rows(const k::Row* rows_abs, const k::Row* rows, SaCol sa, uint32_t cnt, bool mum_mode,
+                                       const std::function<char*(size_t)>& dst_for) {
+    const size_t N = doc_len_.size();
+    hipStream_t st = stream_;
+    order_rows(rows_abs, cnt);
+    d_doc_len_.ensure(N + 1);
+    MMT_HIP(hipMemcpyAsync(d_doc_len_.get(), doc_len_.data(), N * 8, hipMemcpyHostToDevice, st));
+    rk::RowArgs a;
+    a.rows = rows; a.order = d_order_.get(); a.n_rows = cnt; a.sa = sa;
+    a.doc_start = d_doc_start_.get(); a.doc_len = d_doc_len_.get(); a.n_docs = (uint32_t)N; a.revcomp = revcomp_ ? 1 : 0;
+    d_tlen_.ensure(cnt); d_tlen64_.ensure(cnt); d_toff_.ensure(cnt); d_keep_.ensure(cnt);
+    const void *count = d_keep_.get(), *count_sum = nullptr;      // rows kept (MUM) / occurrences (MEM), and their running sum
+    size_t count_width = 4;
+    if (mum_mode) {
+        const size_t slots = (size_t)cnt * N;
+        d_slot_off_.ensure(slots); d_slot_st_.ensure(slots); d_ridx_.ensure(cnt);
+        MMT_HIP(hipMemsetAsync(d_slot_off_.get(), 0xFF, slots * 8, st));     // -1 = document absent
+        MMT_HIP(hipMemsetAsync(d_slot_st_.get(), 0, slots, st));
+        rk::mum_measure(a, d_slot_off_.get(), d_slot_st_.get(), d_keep_.get(), d_tlen_.get(), st);
+        prims::exclusive_sum_u32(d_temp_, d_keep_.get(), d_ridx_.get(), cnt, st);
+        count_sum = d_ridx_.get();
+    } else {
+        // PREFIX.mems rows (write_mem, mem_finder.hpp:210-263): every accepted row is written, occurrences in suffix-array order
+        d_wpos_.ensure(cnt); d_wdoc_.ensure(cnt); d_occ64_.ensure(cnt); d_ooff_.ensure(cnt);
+        rk::mem_measure(a, d_keep_.get() /* occurrences per row */, d_tlen_.get(), d_wpos_.get(), d_wdoc_.get(), st);
+        rk::widen(d_keep_.get(), cnt, d_occ64_.get(), st);
+        prims::exclusive_sum_u64(d_temp_, d_occ64_.get(), d_ooff_.get(), cnt, st);
+        count = d_occ64_.get(); count_sum = d_ooff_.get(); count_width = 8;
+    }
+    rk::widen(d_tlen_.get(), cnt, d_tlen64_.get(), st);
+    prims::exclusive_sum_u64(d_temp_, d_tlen64_.get(), d_toff_.get(), cnt, st);
+    // the totals: last entry of an exclusive sum + the last summand (little endian: a 4-byte entry lands in the low half)
+    uint64_t n0 = 0, n1 = 0, t0 = 0, t1 = 0;
+    auto last = [&](uint64_t* v, const void* d, size_t width) {
+        MMT_HIP(hipMemcpyAsync(v, static_cast<const char*>(d) + (cnt - 1) * width, width, hipMemcpyDeviceToHost, st)); };
+    last(&n0, count_sum, count_width); last(&n1, count, count_width);
+    last(&t0, d_toff_.get(), 8); last(&t1, d_tlen64_.get(), 8);
+    MMT_HIP(hipStreamSynchronize(st));
+    RowsFormat f;
+    f.kept = mum_mode ? (size_t)(n0 + n1) : cnt;
+    f.occ = mum_mode ? 0 : (size_t)(n0 + n1);
+    f.bytes = (size_t)(t0 + t1);
+    char* dst = dst_for(f.bytes);
+    if (!dst) return f;
+    if (mum_mode) {
+        d_olen_.ensure(f.kept + 1); d_ooffs_.ensure(f.kept * N + 1); d_ost_.ensure(f.kept * N + 1);
+        rk::mum_write(a, d_slot_off_.get(), d_slot_st_.get(), d_keep_.get(), d_ridx_.get(), d_toff_.get(), d_olen_.get(),
+                      d_ooffs_.get(), d_ost_.get(), dst, st);
+    } else {
+        d_olen_.ensure(cnt + 1); d_ooffs_.ensure(f.occ + 1); d_omdoc_.ensure(f.occ + 1); d_ost_.ensure(f.occ + 1);
+        rk::mem_write(a, d_ooff_.get(), d_toff_.get(), d_wpos_.get(), d_wdoc_.get(), d_olen_.get(), d_ooffs_.get(),
+                      d_omdoc_.get(), d_ost_.get(), dst, st);
+    }
+    return f;
+}
+
 // ---- the text sink: PREFIX.mums written while the run goes on ---------------------------------------------------------
-void Engine::sink_open(bool mum_mode) {
-    sink_active_ = false;
+void Engine::sink_open() {
     sink_written_path_.clear();
-    sink_mum_ = mum_mode;
     sink_total_rows_ = 0;
     if (sink_path_.empty() || std::getenv("MUMEMTO_NO_TEXT_SINK")) return;
     // Rows that have been written need not stay: with a sink, a run whose accepted rows would not fit the device next to
@@ -845,206 +904,61 @@ void Engine::sink_open(bool mum_mode) {
     sink_discard_ = sink_force_discard_ ||
                     (!sink_keep_rows_ &&
                      (std::getenv("MMT_SINK_DISCARD") ? std::atoi(std::getenv("MMT_SINK_DISCARD")) != 0 : (packed_ || n_ >= (1ull << 37))));
-    if (!mum_mode && !sink_discard_) return;          // (a MEM run that keeps its rows writes its file at the end, as before)
-    // the bytes go to PREFIX.mums.tmp and take the final name when the run has succeeded (sink_close): a run that fails
-    // after some windows -- out of memory, a consistency check at the end -- must not leave a plausible partial PREFIX.mums
+    if (!rows_.mum_mode && !sink_discard_) return;          // (a MEM run that keeps its rows writes its file at the end, as before)
     // ("/dev/null": the bytes are formatted, copied out, digested and dropped -- a full-size test run whose 66 GB of rows the
     // box has no room for)
-    // (any path that exists and is not a regular file -- a FIFO, /dev/stdout -- is written in place as well: the same rule as
-    // merge.cpp write_merged_text)
-    {
-        struct stat sb;
-        sink_null_ = sink_path_ == "/dev/null" || (::stat(sink_path_.c_str(), &sb) == 0 && !S_ISREG(sb.st_mode));
-    }
-    sink_tmp_path_ = sink_null_ ? sink_path_ : sink_path_ + ".tmp";
-    sink_digest_ = StreamDigest(); sink_written_ = 0; sink_digest_value_ = 0;
-    sink_want_digest_ = std::getenv("MMT_SINK_DIGEST") != nullptr;
-    sink_fd_ = ::open(sink_tmp_path_.c_str(), sink_null_ ? O_WRONLY : (O_CREAT | O_TRUNC | O_WRONLY), 0644);
-    if (sink_fd_ < 0) throw std::runtime_error("cannot write " + sink_tmp_path_);
-    sink_rows_done_ = 0; sink_bytes_ = 0; sink_block_at_ = 0; sink_block_used_ = 0;
-    sink_block_pending_.assign(sink_blocks_.size(), 0);
-    sink_closing_ = false; sink_error_.clear();
+    sink_writer_.open(sink_path_, device_, std::getenv("MMT_SINK_DIGEST") != nullptr);
+    sink_rows_done_ = 0;
     sink_pieces_ = 0;
     if (!sink_stream_) {
         MMT_HIP(hipStreamCreateWithFlags(&sink_stream_, hipStreamNonBlocking));
         for (auto& ev : sink_copied_) MMT_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     }
-    sink_active_ = true;
-    const int device = device_;
-    sink_thread_ = std::thread([this, device]() {
-        (void)hipSetDevice(device);
-        for (;;) {
-            SinkPiece pc;
-            {
-                std::unique_lock<std::mutex> lk(sink_mu_);
-                sink_cv_.wait(lk, [&] { return !sink_q_.empty() || sink_closing_; });
-                if (sink_q_.empty()) break;
-                pc = sink_q_.front(); sink_q_.pop_front();
-            }
-            // (sink_error_ is read by the run's thread in sink_host_room / sink_close: both sides under the mutex)
-            auto failed = [&]() { std::lock_guard<std::mutex> lk(sink_mu_); return !sink_error_.empty(); };
-            auto fail_with = [&](const std::string& what) { std::lock_guard<std::mutex> lk(sink_mu_); if (sink_error_.empty()) sink_error_ = what; };
-            if (hipEventSynchronize(pc.ready) != hipSuccess) fail_with("device copy of the output failed");
-            (void)hipEventDestroy(pc.ready);
-            for (size_t done = 0; !failed() && done < pc.n;) {
-                const ssize_t w = ::write(sink_fd_, pc.p + done, pc.n - done);
-                if (w <= 0) { fail_with("short write to " + sink_tmp_path_); break; }
-                done += (size_t)w;
-            }
-            // a running digest of the bytes in file order (this one thread writes the pieces in order; whole words are carried
-            // across piece boundaries, which fall where windows end and differ from box to box): what two runs of a file
-            // nobody can keep are compared by
-            if (sink_null_ || sink_want_digest_) sink_digest_.update(pc.p, pc.n);
-            { std::lock_guard<std::mutex> lk(sink_mu_); sink_written_ += pc.n; }
-            { std::lock_guard<std::mutex> lk(sink_mu_); sink_block_pending_[pc.block]--; }
-            sink_cv_.notify_all();
-        }
-    });
-}
-// Page-locked room for a piece: a RING of blocks of 256 MB (or the piece) that stay with the engine.  A block is used
-// again once the writer thread has written every piece in it, so the page-locked memory of a run is a few blocks however
-// large the output is (round 3 kept every piece until the end of the run: 4.5 GB of pinned memory for a rank's share of
-// whole genomes, and it stayed with the engine).
-char* Engine::sink_host_room(size_t n, uint32_t* block) {
-    // (64 MB: page-locking costs 0.19 s per GB when the block is made and 0.13 s per GB when the process ends -- the four
-    // blocks of 256 MB were a quarter of a second of the bench workload's 2.2 s from process start to exit)
-    static const size_t BLOCK = (size_t)(std::getenv("MMT_SINK_BLOCK_MB") ? std::max(1, std::atoi(std::getenv("MMT_SINK_BLOCK_MB"))) : 64) << 20;
-    const size_t RING = 4;
-    auto fits = [&](size_t b) { return std::max(BLOCK, sink_block_cap_[b]) >= n; };
-    std::unique_lock<std::mutex> lk(sink_mu_);
-    if (!sink_blocks_.empty() && sink_block_at_ < sink_blocks_.size() && fits(sink_block_at_) &&
-        sink_block_used_ + n <= std::max(BLOCK, sink_block_cap_[sink_block_at_])) {
-        char* p = sink_blocks_[sink_block_at_]->get() + sink_block_used_;
-        sink_block_used_ += n; sink_block_pending_[sink_block_at_]++; *block = (uint32_t)sink_block_at_;
-        return p;
-    }
-    // the next block of the ring: a new one while the ring is short, otherwise the oldest, once it has been written
-    size_t next;
-    if (sink_blocks_.size() < RING) {
-        next = sink_blocks_.size();
-        sink_blocks_.emplace_back(new PinnedBuf<char>());
-        sink_block_cap_.push_back(0);
-        sink_block_pending_.push_back(0);
-    } else {
-        next = (sink_block_at_ + 1) % sink_blocks_.size();
-        sink_cv_.wait(lk, [&] { return sink_block_pending_[next] == 0 || !sink_error_.empty(); });
-    }
-    if (sink_block_cap_[next] < std::max(BLOCK, n)) {
-        lk.unlock();
-        sink_blocks_[next]->ensure(std::max(BLOCK, n));      // (nobody reads an idle block)
-        lk.lock();
-        sink_block_cap_[next] = std::max(BLOCK, n);
-    }
-    sink_block_at_ = next; sink_block_used_ = n; sink_block_pending_[next]++; *block = (uint32_t)next;
-    return sink_blocks_[next]->get();
 }
 // the rows accepted since the last call, in pop order, as PREFIX.mums bytes -> helper thread
 void Engine::sink_flush(ScanState& S) {
-    if (!sink_active_) return;
+    if (!sink_writer_.active()) return;
     const size_t r0 = sink_rows_done_, r1 = S.rows_used;
     if (r1 <= r0) return;
-    const uint32_t cnt = (uint32_t)(r1 - r0);
-    const size_t N = doc_len_.size();
     hipStream_t st = stream_;
-    order_rows(d_rows_.get() + r0, cnt);
-    d_doc_len_.ensure(N + 1);
-    MMT_HIP(hipMemcpyAsync(d_doc_len_.get(), doc_len_.data(), N * 8, hipMemcpyHostToDevice, st));
-    rk::RowArgs a;
-    a.rows = d_rows_pool_.get() + r0; a.order = d_order_.get(); a.n_rows = cnt;
-    a.sa.lo = d_pool_lo_.get(); a.sa.hi = wide_ ? d_pool_hi_.get() : nullptr;
-    a.doc_start = d_doc_start_.get(); a.doc_len = d_doc_len_.get(); a.n_docs = (uint32_t)N; a.revcomp = revcomp_ ? 1 : 0;
-    d_tlen_.ensure(cnt); d_tlen64_.ensure(cnt); d_toff_.ensure(cnt); d_keep_.ensure(cnt);
-    size_t kept = 0, tbytes = 0, occ = 0;
-    if (sink_mum_) {
-        const size_t slots = (size_t)cnt * N;
-        d_slot_off_.ensure(slots); d_slot_st_.ensure(slots); d_ridx_.ensure(cnt);
-        MMT_HIP(hipMemsetAsync(d_slot_off_.get(), 0xFF, slots * 8, st));     // -1 = document absent
-        MMT_HIP(hipMemsetAsync(d_slot_st_.get(), 0, slots, st));
-        rk::mum_measure(a, d_slot_off_.get(), d_slot_st_.get(), d_keep_.get(), d_tlen_.get(), st);
-        prims::exclusive_sum_u32(d_temp_, d_keep_.get(), d_ridx_.get(), cnt, st);
-        rk::widen(d_tlen_.get(), cnt, d_tlen64_.get(), st);
-        prims::exclusive_sum_u64(d_temp_, d_tlen64_.get(), d_toff_.get(), cnt, st);
-        uint32_t k0 = 0, k1 = 0; uint64_t t0 = 0, t1 = 0;
-        MMT_HIP(hipMemcpyAsync(&k0, d_ridx_.get() + (cnt - 1), 4, hipMemcpyDeviceToHost, st));
-        MMT_HIP(hipMemcpyAsync(&k1, d_keep_.get() + (cnt - 1), 4, hipMemcpyDeviceToHost, st));
-        MMT_HIP(hipMemcpyAsync(&t0, d_toff_.get() + (cnt - 1), 8, hipMemcpyDeviceToHost, st));
-        MMT_HIP(hipMemcpyAsync(&t1, d_tlen64_.get() + (cnt - 1), 8, hipMemcpyDeviceToHost, st));
-        MMT_HIP(hipStreamSynchronize(st));
-        kept = (size_t)k0 + k1; tbytes = (size_t)(t0 + t1);
-    } else {
-        // PREFIX.mems rows (write_mem, mem_finder.hpp:210-263): every accepted row is written, occurrences in suffix-array order
-        d_wpos_.ensure(cnt); d_wdoc_.ensure(cnt); d_occ64_.ensure(cnt); d_ooff_.ensure(cnt);
-        rk::mem_measure(a, d_keep_.get() /* occurrences per row */, d_tlen_.get(), d_wpos_.get(), d_wdoc_.get(), st);
-        rk::widen(d_keep_.get(), cnt, d_occ64_.get(), st);
-        prims::exclusive_sum_u64(d_temp_, d_occ64_.get(), d_ooff_.get(), cnt, st);
-        rk::widen(d_tlen_.get(), cnt, d_tlen64_.get(), st);
-        prims::exclusive_sum_u64(d_temp_, d_tlen64_.get(), d_toff_.get(), cnt, st);
-        uint64_t o0 = 0, o1 = 0, t0 = 0, t1 = 0;
-        MMT_HIP(hipMemcpyAsync(&o0, d_ooff_.get() + (cnt - 1), 8, hipMemcpyDeviceToHost, st));
-        MMT_HIP(hipMemcpyAsync(&o1, d_occ64_.get() + (cnt - 1), 8, hipMemcpyDeviceToHost, st));
-        MMT_HIP(hipMemcpyAsync(&t0, d_toff_.get() + (cnt - 1), 8, hipMemcpyDeviceToHost, st));
-        MMT_HIP(hipMemcpyAsync(&t1, d_tlen64_.get() + (cnt - 1), 8, hipMemcpyDeviceToHost, st));
-        MMT_HIP(hipStreamSynchronize(st));
-        kept = cnt; occ = (size_t)(o0 + o1); tbytes = (size_t)(t0 + t1);
-    }
-    sink_rows_done_ = r1;
-    sink_total_rows_ += kept;
-    auto discard = [&]() {
-        // the rows and their suffix-array entries are dead once their bytes are formatted: the next window starts at slot 0
-        if (!sink_discard_) return;
-        MMT_HIP(hipMemsetAsync(d_count_.get() + 1, 0, 4, st));
-        S.rows_used = 0; sink_rows_done_ = 0; pool_used_ = 0;
-    };
-    if (!tbytes) { discard(); return; }
     // the piece is formatted on the run's stream and copied out on the copy stream (two device pieces in turn: the
     // formatting of a piece waits for the copy of the piece two flushes ago)
     const uint32_t slot_i = sink_pieces_ & 1u;
     DevBuf<char>& piece = d_piece_[slot_i];
-    if (sink_pieces_ >= 2) MMT_HIP(hipStreamWaitEvent(st, sink_copied_[slot_i], 0));
-    if (piece.size() < tbytes + 1) { MMT_HIP(hipStreamSynchronize(sink_stream_)); piece.ensure(tbytes + tbytes / 4 + 1); }
-    if (sink_mum_) {
-        d_olen_.ensure(kept + 1); d_ooffs_.ensure(kept * N + 1); d_ost_.ensure(kept * N + 1);
-        rk::mum_write(a, d_slot_off_.get(), d_slot_st_.get(), d_keep_.get(), d_ridx_.get(), d_toff_.get(), d_olen_.get(),
-                      d_ooffs_.get(), d_ost_.get(), piece.get(), st);
-    } else {
-        d_olen_.ensure(cnt + 1); d_ooffs_.ensure(occ + 1); d_omdoc_.ensure(occ + 1); d_ost_.ensure(occ + 1);
-        rk::mem_write(a, d_ooff_.get(), d_toff_.get(), d_wpos_.get(), d_wdoc_.get(), d_olen_.get(), d_ooffs_.get(),
-                      d_omdoc_.get(), d_ost_.get(), piece.get(), st);
+    SaCol pool;
+    pool.lo = d_pool_lo_.get(); pool.hi = wide_ ? d_pool_hi_.get() : nullptr;
+    const RowsFormat f = format_rows(d_rows_.get() + r0, d_rows_pool_.get() + r0, pool, (uint32_t)(r1 - r0), rows_.mum_mode,
+                                     [&](size_t bytes) -> char* {
+        if (!bytes) return nullptr;
+        if (sink_pieces_ >= 2) MMT_HIP(hipStreamWaitEvent(st, sink_copied_[slot_i], 0));
+        if (piece.size() < bytes + 1) { MMT_HIP(hipStreamSynchronize(sink_stream_)); piece.ensure(bytes + bytes / 4 + 1); }
+        return piece.get();
+    });
+    sink_rows_done_ = r1;
+    sink_total_rows_ += f.kept;
+    if (sink_discard_) {
+        // the rows and their suffix-array entries are dead once their bytes are formatted: the next window starts at slot 0
+        MMT_HIP(hipMemsetAsync(d_count_.get() + 1, 0, 4, st));
+        S.rows_used = 0; sink_rows_done_ = 0; pool_used_ = 0;
     }
-    discard();
-    SinkPiece pc;
-    pc.n = tbytes;
-    char* h = sink_host_room(tbytes, &pc.block);
-    pc.p = h;
+    if (!f.bytes) return;
+    PieceWriter::Piece pc = sink_writer_.room(f.bytes);
     hipEvent_t formatted;
     MMT_HIP(hipEventCreateWithFlags(&formatted, hipEventDisableTiming));
     MMT_HIP(hipEventRecord(formatted, st));
     MMT_HIP(hipStreamWaitEvent(sink_stream_, formatted, 0));
-    MMT_HIP(hipMemcpyAsync(h, piece.get(), tbytes, hipMemcpyDeviceToHost, sink_stream_));
+    MMT_HIP(hipMemcpyAsync(pc.p, piece.get(), f.bytes, hipMemcpyDeviceToHost, sink_stream_));
     MMT_HIP(hipEventRecord(sink_copied_[slot_i], sink_stream_));
     MMT_HIP(hipEventCreateWithFlags(&pc.ready, hipEventDisableTiming));
     MMT_HIP(hipEventRecord(pc.ready, sink_stream_));
     (void)hipEventDestroy(formatted);
     sink_pieces_++;
-    { std::lock_guard<std::mutex> lk(sink_mu_); sink_q_.push_back(pc); }
-    sink_cv_.notify_one();
-    sink_bytes_ += tbytes;
+    sink_writer_.push(pc);
 }
 void Engine::sink_close(bool ok) {
-    if (!sink_active_) return;
-    { std::lock_guard<std::mutex> lk(sink_mu_); sink_closing_ = true; }
-    sink_cv_.notify_one();
-    if (sink_thread_.joinable()) sink_thread_.join();
+    if (!sink_writer_.active()) return;
     (void)hipStreamSynchronize(sink_stream_);
-    std::string error;
-    { std::lock_guard<std::mutex> lk(sink_mu_); error = sink_error_; }
-    if (sink_fd_ >= 0 && ::close(sink_fd_) != 0 && error.empty()) error = "cannot close " + sink_tmp_path_;
-    sink_fd_ = -1;
-    sink_active_ = false;
-    if (error.empty() && !ok) error = "the run failed";
-    if (error.empty() && !sink_null_ && std::rename(sink_tmp_path_.c_str(), sink_path_.c_str()) != 0) error = "cannot rename " + sink_tmp_path_;
-    if (!error.empty()) { if (!sink_null_) ::unlink(sink_tmp_path_.c_str()); throw std::runtime_error(error); }
-    sink_digest_value_ = sink_digest_.final();
+    sink_writer_.close(ok);
     sink_written_path_ = sink_path_;
     sink_discarded_ = sink_discard_;
 }
@@ -1052,19 +966,20 @@ void Engine::sink_close(bool ok) {
 void Engine::make_rows(const mmt_params& p) {
     // Rows stay on the device: sort into pop order, measure, place, write (rows_kernels.hip), then
     // one D2H of the library arrays and of the .mums / .mems bytes into page-locked host memory.
-    const size_t N = doc_len_.size();
     hipStream_t st = stream_;
     ev_[5]->start(st);
     HostRows& R = rows_;
     R = HostRows();
     R.mum_mode = p.max_doc_freq == 1;                 // mem_finder.hpp:85
-    R.n_docs = N;
+    R.n_docs = doc_len_.size();
     bumbl_.clear();
+    h_occ_start_.ensure(2);
+    h_occ_start_.get()[0] = 0;
+    R.occ_start = h_occ_start_.get();
+    rows_pending_ = 0;
     if (sink_discarded_ && !sink_written_path_.empty()) {
         // the rows left with the windows that accepted them (sink_flush): the file and the count are what this run answers for
         R.n_rows = sink_total_rows_;
-        h_occ_start_.ensure(2); h_occ_start_.get()[0] = 0; R.occ_start = h_occ_start_.get();
-        rows_pending_ = 0;
         ev_[5]->stop(st);
         return;
     }
@@ -1074,71 +989,20 @@ void Engine::make_rows(const mmt_params& p) {
         MMT_HIP(hipStreamSynchronize(st));
         return v;
     }();
-    h_occ_start_.ensure(2);
-    h_occ_start_.get()[0] = 0;
-    R.occ_start = h_occ_start_.get();
     if (n_rows == 0) { ev_[5]->stop(st); return; }
-
-    // pop order of the reference's stack: closing position ascending, longer first
-    order_rows(d_rows_.get(), n_rows);
-    d_doc_len_.ensure(N + 1);
-    MMT_HIP(hipMemcpyAsync(d_doc_len_.get(), doc_len_.data(), N * 8, hipMemcpyHostToDevice, st));
-    rk::RowArgs a;
-    a.rows = d_rows_.get(); a.order = d_order_.get(); a.n_rows = n_rows; a.sa = sa_col();
-    if (streamed_) {            // the columns are gone: the rows index the pool of their own suffix-array entries
-        a.rows = d_rows_pool_.get();
-        a.sa.lo = d_pool_lo_.get(); a.sa.hi = wide_ ? d_pool_hi_.get() : nullptr;
-    }
-    a.doc_start = d_doc_start_.get(); a.doc_len = d_doc_len_.get(); a.n_docs = (uint32_t)N; a.revcomp = revcomp_ ? 1 : 0;
-    d_tlen_.ensure(n_rows); d_tlen64_.ensure(n_rows); d_toff_.ensure(n_rows);
-    auto last_u32 = [&](const uint32_t* d) {
-        uint32_t v = 0; MMT_HIP(hipMemcpyAsync(&v, d + (n_rows - 1), 4, hipMemcpyDeviceToHost, st)); return v; };
-    auto last_u64 = [&](const uint64_t* d) {
-        uint64_t v = 0; MMT_HIP(hipMemcpyAsync(&v, d + (n_rows - 1), 8, hipMemcpyDeviceToHost, st)); return v; };
-
-    if (R.mum_mode) {
-        const size_t slots = (size_t)n_rows * N;
-        d_slot_off_.ensure(slots); d_slot_st_.ensure(slots); d_keep_.ensure(n_rows); d_ridx_.ensure(n_rows);
-        MMT_HIP(hipMemsetAsync(d_slot_off_.get(), 0xFF, slots * 8, st));     // -1 = document absent
-        MMT_HIP(hipMemsetAsync(d_slot_st_.get(), 0, slots, st));
-        rk::mum_measure(a, d_slot_off_.get(), d_slot_st_.get(), d_keep_.get(), d_tlen_.get(), st);
-        prims::exclusive_sum_u32(d_temp_, d_keep_.get(), d_ridx_.get(), n_rows, st);
-        rk::widen(d_tlen_.get(), n_rows, d_tlen64_.get(), st);
-        prims::exclusive_sum_u64(d_temp_, d_tlen64_.get(), d_toff_.get(), n_rows, st);
-        const uint32_t k0 = last_u32(d_ridx_.get()), k1 = last_u32(d_keep_.get());
-        const uint64_t t0 = last_u64(d_toff_.get()), t1 = last_u64(d_tlen64_.get());
-        MMT_HIP(hipStreamSynchronize(st));
-        const size_t kept = (size_t)k0 + k1, tbytes = (size_t)(t0 + t1);
-        d_olen_.ensure(kept + 1); d_ooffs_.ensure(kept * N + 1); d_ost_.ensure(kept * N + 1); d_otext_.ensure(tbytes + 1);
-        rk::mum_write(a, d_slot_off_.get(), d_slot_st_.get(), d_keep_.get(), d_ridx_.get(), d_toff_.get(),
-                      d_olen_.get(), d_ooffs_.get(), d_ost_.get(), d_otext_.get(), st);
-        // the tables and the bytes stay in HBM; fetch_rows() copies what a caller asks for (library arrays, file bytes)
-        R.n_rows = kept; R.text_len = tbytes;
-        rows_pending_ = kept ? (ROWS_ARRAYS | ROWS_TEXT) : 0;
-    } else {
-        d_keep_.ensure(n_rows); d_wpos_.ensure(n_rows); d_wdoc_.ensure(n_rows); d_occ64_.ensure(n_rows);
-        d_ooff_.ensure(n_rows);
-        rk::mem_measure(a, d_keep_.get() /* occurrences per row */, d_tlen_.get(), d_wpos_.get(), d_wdoc_.get(), st);
-        rk::widen(d_keep_.get(), n_rows, d_occ64_.get(), st);
-        prims::exclusive_sum_u64(d_temp_, d_occ64_.get(), d_ooff_.get(), n_rows, st);
-        rk::widen(d_tlen_.get(), n_rows, d_tlen64_.get(), st);
-        prims::exclusive_sum_u64(d_temp_, d_tlen64_.get(), d_toff_.get(), n_rows, st);
-        const uint64_t o0 = last_u64(d_ooff_.get()), o1 = last_u64(d_occ64_.get());
-        const uint64_t t0 = last_u64(d_toff_.get()), t1 = last_u64(d_tlen64_.get());
-        MMT_HIP(hipStreamSynchronize(st));
-        const size_t occ = (size_t)(o0 + o1), tbytes = (size_t)(t0 + t1);
-        d_olen_.ensure(n_rows); d_ooffs_.ensure(occ + 1); d_omdoc_.ensure(occ + 1); d_ost_.ensure(occ + 1);
-        d_otext_.ensure(tbytes + 1);
-        rk::mem_write(a, d_ooff_.get(), d_toff_.get(), d_wpos_.get(), d_wdoc_.get(), d_olen_.get(), d_ooffs_.get(),
-                      d_omdoc_.get(), d_ost_.get(), d_otext_.get(), st);
-        R.n_rows = n_rows; R.n_occ = occ; R.text_len = tbytes;
-        rows_pending_ = ROWS_ARRAYS | ROWS_TEXT;
-    }
+    // (a streamed run: the columns are gone, the rows index the pool of their own suffix-array entries)
+    SaCol sa = sa_col();
+    if (streamed_) { sa.lo = d_pool_lo_.get(); sa.hi = wide_ ? d_pool_hi_.get() : nullptr; }
+    const RowsFormat f = format_rows(d_rows_.get(), streamed_ ? d_rows_pool_.get() : d_rows_.get(), sa, n_rows, R.mum_mode,
+                                     [&](size_t bytes) { d_otext_.ensure(bytes + 1); return d_otext_.get(); });
+    // the tables and the bytes stay in HBM; fetch_rows() copies what a caller asks for (library arrays, file bytes)
+    R.n_rows = f.kept; R.n_occ = f.occ; R.text_len = f.bytes;
+    rows_pending_ = f.kept ? (ROWS_ARRAYS | ROWS_TEXT) : 0;
     ev_[5]->stop(st);
 }
 
-// D2H of the last run's rows into page-locked host memory, on demand: the library arrays (ROWS_ARRAYS) and / or the
-// bytes of PREFIX.mums / PREFIX.mems (ROWS_TEXT).
+// PREFIX.mums / .mems of the last run to a file: the bytes leave HBM in pieces and every piece is written while the next
+// ones are still on their way (the complete host copy stays behind as rows(ROWS_TEXT))
 void Engine::write_text_file(const std::string& path) {
     if (!sink_written_path_.empty() && sink_written_path_ == path) return;      // written while the run went on (set_text_sink)
     if (!(rows_pending_ & ROWS_TEXT) || merged_thresh_valid_) {      // already on the host (or a merged result: staged)
@@ -1148,6 +1012,8 @@ void Engine::write_text_file(const std::string& path) {
     }
     MMT_HIP(hipSetDevice(device_));
     HostRows& R = rows_;
+    OutFile out;
+    out.open(path, OutFile::IN_PLACE);
     h_text_.ensure(R.text_len + 1);
     const size_t PIECE = (size_t)64 << 20;
     const size_t pieces = (R.text_len + PIECE - 1) / PIECE;
@@ -1158,25 +1024,18 @@ void Engine::write_text_file(const std::string& path) {
         MMT_HIP(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
         MMT_HIP(hipEventRecord(ev[k], stream_));
     }
-    const int fd = ::open(path.c_str(), O_CREAT | O_TRUNC | O_WRONLY, 0644);
-    std::string error;
-    if (fd < 0) error = "cannot write " + path;
     for (size_t k = 0; k < pieces; k++) {
         MMT_HIP(hipEventSynchronize(ev[k]));
         (void)hipEventDestroy(ev[k]);
-        const size_t at = k * PIECE, len = std::min(PIECE, R.text_len - at);
-        for (size_t done = 0; error.empty() && done < len;) {
-            const ssize_t w = ::write(fd, h_text_.get() + at + done, len - done);
-            if (w <= 0) { error = "short write to " + path; break; }
-            done += (size_t)w;
-        }
+        out.write_all(h_text_.get() + k * PIECE, std::min(PIECE, R.text_len - k * PIECE));
     }
-    if (fd >= 0 && ::close(fd) != 0 && error.empty()) error = "cannot close " + path;
     R.text = h_text_.get();
     rows_pending_ &= ~ROWS_TEXT;
-    if (!error.empty()) throw std::runtime_error(error);
+    out.commit();
 }
 
+// D2H of the last run's rows into page-locked host memory, on demand: the library arrays (ROWS_ARRAYS) and / or the
+// bytes of PREFIX.mums / PREFIX.mems (ROWS_TEXT).
 void Engine::fetch_rows(int need) {
     // the rows of a run that wrote them window by window and dropped them (set_text_sink over a text that fills the device,
     // or the pieces of a sharded run) are in the file and nowhere else: say so instead of handing out null arrays
@@ -1420,13 +1279,12 @@ void Engine::run(const mmt_params& p) {
     ScanState S;
     scan_begin(p, S);
     streamed_ = true;
-    sink_open(p.max_doc_freq == 1);
+    sink_open();
     try {
         if (pfp_->guided) guided_stream(S, p); else pfp_stream(S, p);
         sink_flush(S);
     } catch (...) {
         try { sink_close(false); } catch (...) {}
-        sink_written_path_.clear();
         throw;
     }
     sink_close();

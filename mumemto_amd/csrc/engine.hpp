@@ -1,13 +1,10 @@
 // engine.hpp -- the hot path as one object: text -> SA/LCP/BWT -> scan -> rows.
 #pragma once
-#include <condition_variable>
 #include <cstdint>
 #include <cstring>
-#include <deque>
+#include <functional>
 #include <memory>
-#include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/mumemto_gpu.h"
@@ -15,6 +12,7 @@
 #include "kernels.hpp"
 #include "merge_types.hpp"
 #include "pfp.hpp"
+#include "piece_writer.hpp"
 #include "sorter.hpp"
 #include "textref.hpp"
 
@@ -194,7 +192,7 @@ public:
     int kmer_in_share(const uint8_t* kmer, size_t k) const;        // (guided.cpp)
     // (bytes written, digest of those bytes in file order) of the last run's sink; the digest is kept when the sink is
     // "/dev/null" -- a test run whose rows nobody can keep -- or MMT_SINK_DIGEST is set
-    void text_sink_digest(uint64_t out[2]) const { out[0] = sink_written_; out[1] = sink_digest_value_; }
+    void text_sink_digest(uint64_t out[2]) const { out[0] = sink_writer_.written(); out[1] = sink_writer_.digest(); }
     void write_text_file(const std::string& path);
     // The row tap (tests/bigchecks.py check_bins_complete): every accepted interval of the NEXT runs whose match begins with
     // one of the given k-mers (k <= 16 characters each) leaves a copy of its length and all its suffix-array entries before
@@ -345,21 +343,6 @@ private:
     DevBuf<k::Row> d_rows_pool_;
     DevBuf<uint64_t> d_cap_cnt_, d_cap_off_;
     uint64_t pool_used_ = 0;
-    // digest of a byte stream that arrives in pieces of any size (the text sink's bytes in file order)
-    struct StreamDigest {
-        uint64_t h = 0x6d756d656d746f35ull;
-        uint8_t carry[8];
-        uint32_t have = 0;
-        void word(uint64_t w) { h = (h ^ w) * 0x9E3779B97F4A7C15ull; h ^= h >> 29; }
-        void update(const char* p, size_t n) {
-            size_t i = 0;
-            while (have && have < 8 && i < n) carry[have++] = (uint8_t)p[i++];
-            if (have == 8) { uint64_t w; std::memcpy(&w, carry, 8); word(w); have = 0; }
-            for (; i + 8 <= n; i += 8) { uint64_t w; std::memcpy(&w, p + i, 8); word(w); }
-            for (; i < n; i++) carry[have++] = (uint8_t)p[i];
-        }
-        uint64_t final() const { uint64_t x = h; for (uint32_t i = 0; i < have; i++) x = (x ^ carry[i]) * 0x100000001b3ull; return x ^ (x >> 31); }
-    };
     // the row tap (set_row_tap)
     std::vector<uint64_t> tap_kmers_;            // 2 words per k-mer
     uint32_t tap_k_ = 0;
@@ -367,35 +350,23 @@ private:
     DevBuf<uint64_t> d_tap_kmers_, d_tap_off_, d_tap_sa_, d_tap_used_;
     DevBuf<uint32_t> d_tap_len_, d_tap_cnt_;
     void tap_window(const k::Row* rows, uint32_t n_rows, SaCol pool);
-    // the text sink (set_text_sink)
-    bool sink_force_discard_ = false, sink_keep_rows_ = false, sink_null_ = false, sink_want_digest_ = false;
-    StreamDigest sink_digest_;
-    uint64_t sink_digest_value_ = 0, sink_written_ = 0;
-    struct SinkPiece { const char* p; size_t n; hipEvent_t ready; uint32_t block; };
-    std::string sink_path_, sink_written_path_, sink_tmp_path_;
-    bool sink_active_ = false, sink_mum_ = true, sink_discard_ = false, sink_discarded_ = false;
+    // the text sink (set_text_sink): what the run decides, the device pieces, the writer behind them
+    std::string sink_path_, sink_written_path_;
+    bool sink_force_discard_ = false, sink_keep_rows_ = false, sink_discard_ = false, sink_discarded_ = false;
     uint64_t sink_total_rows_ = 0;
-    int sink_fd_ = -1;
     size_t sink_rows_done_ = 0;
-    uint64_t sink_bytes_ = 0;
-    std::thread sink_thread_;
-    std::mutex sink_mu_;
-    std::condition_variable sink_cv_;
-    std::deque<SinkPiece> sink_q_;
-    bool sink_closing_ = false;
-    std::string sink_error_;
-    std::vector<std::unique_ptr<PinnedBuf<char>>> sink_blocks_;      // page-locked blocks, kept between runs
-    std::vector<size_t> sink_block_cap_;
-    std::vector<uint32_t> sink_block_pending_;     // pieces of a block the writer thread has not written yet (under sink_mu_)
-    size_t sink_block_at_ = 0, sink_block_used_ = 0;
+    PieceWriter sink_writer_;               // a ring of four page-locked blocks that stay with the engine between runs
     DevBuf<char> d_piece_[2];                // two pieces: one is copied out on the copy stream while the next is formatted
     hipStream_t sink_stream_ = nullptr;
     hipEvent_t sink_copied_[2] = {nullptr, nullptr};
     uint32_t sink_pieces_ = 0;
-    void sink_open(bool mum_mode);
+    void sink_open();
     void sink_flush(ScanState& S);
     void sink_close(bool ok = true);        // ok: PREFIX.mums.tmp takes its name; otherwise it is removed
-    char* sink_host_room(size_t n, uint32_t* block);
+    // `cnt` rows in pop order as row tables (d_olen_, d_ooffs_, ...) and as bytes at dst_for(bytes) (null: not written)
+    struct RowsFormat { size_t kept = 0, occ = 0, bytes = 0; };
+    RowsFormat format_rows(const k::Row* rows_abs, const k::Row* rows, SaCol sa, uint32_t cnt, bool mum_mode,
+                           const std::function<char*(size_t)>& dst_for);
     void order_rows(const k::Row* rows_abs, uint32_t cnt);
     float emit_ms_ = 0.f;
     uint64_t stream_entries_ = 0, window_bytes_peak_ = 0;

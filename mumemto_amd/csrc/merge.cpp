@@ -13,14 +13,10 @@
 #include <cstdlib>
 #include <memory>
 #include <stdexcept>
-#include <condition_variable>
-#include <deque>
-#include <fcntl.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
 #include "kernels.hpp"
 #include "merge_kernels.hpp"
+#include "piece_writer.hpp"
 #include "pfp_kernels.hpp"
 #include "prims.hpp"
 
@@ -506,7 +502,7 @@ const char* stage_merged_text(Engine& e, const MergedRows& m, size_t* n_bytes) {
 // merged table of 94 whole genomes is 40 million rows x 94 columns = tens of GB of text: it is formatted in pieces of
 // whole rows -- row ranges cut where the running byte offset passes a multiple of the piece size --, every piece into one
 // of two device buffers, copied to one of two page-locked blocks and written by a helper thread while the next piece is
-// formatted (the shape of the text sink of a streamed run, engine.cpp).
+// formatted (PieceWriter).
 static constexpr size_t MERGED_TEXT_ONE_PIECE = (size_t)3 << 30, MERGED_TEXT_PIECE = (size_t)1 << 30;
 
 void write_merged_text(Engine& e, const MergedRows& m, const std::string& path) {
@@ -544,66 +540,20 @@ void write_merged_text(Engine& e, const MergedRows& m, const std::string& path) 
         r = q;
     }
     DevBuf<char> d_piece[2];
-    PinnedBuf<char> h_piece[2];
-    for (int b = 0; b < 2; b++) { d_piece[b].ensure(longest + 1); h_piece[b].ensure(longest + 1); }
-    // the bytes go to PATH.tmp and take the final name when every piece is in (a short write, a full disk or a kill half way
-    // must not leave a plausible but truncated PREFIX.mums); a device file -- /dev/null: runs that only time the formatting --
-    // is written as it is
-    struct stat sb;
-    const bool special = ::stat(path.c_str(), &sb) == 0 && !S_ISREG(sb.st_mode);
-    const std::string tmp = special ? path : path + ".tmp";
-    const int fd = ::open(tmp.c_str(), special ? O_WRONLY : (O_CREAT | O_TRUNC | O_WRONLY), 0644);
-    if (fd < 0) throw std::runtime_error("cannot write " + tmp);
-    // the writer: piece i of buffer i & 1 once its copy has landed
-    struct Job { int buf; size_t bytes; };
-    std::mutex mu; std::condition_variable cv; std::deque<Job> q; bool closing = false; int free_buf[2] = {1, 1};
-    std::string error;
-    std::thread writer([&]() {
-        for (;;) {
-            Job j;
-            { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return !q.empty() || closing; });
-              if (q.empty()) return;
-              j = q.front(); q.pop_front(); }
-            const char* src = h_piece[j.buf].get();
-            size_t at = 0;
-            auto failed = [&]() { std::lock_guard<std::mutex> lk(mu); return !error.empty(); };     // (read and written under the mutex)
-            while (at < j.bytes && !failed()) {
-                const ssize_t w = ::write(fd, src + at, j.bytes - at);
-                if (w <= 0) { std::lock_guard<std::mutex> lk(mu); error = "short write to " + tmp; break; }
-                at += (size_t)w;
-            }
-            { std::lock_guard<std::mutex> lk(mu); free_buf[j.buf] = 1; }
-            cv.notify_all();
-        }
-    });
-    try {
-        for (size_t i = 0; i + 1 < cut.size(); i++) {
-            const int b = (int)(i & 1);
-            const size_t r0 = cut[i], r1 = cut[i + 1];
-            const uint64_t bytes = h_off[r1] - h_off[r0];
-            { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return free_buf[b] == 1; }); free_buf[b] = 0;
-              if (!error.empty()) throw std::runtime_error(error); }
-            mk::table_write(m.d_length.get() + r0, m.d_offsets.get() + r0 * m.n_docs, m.d_strands.get() + r0 * m.n_docs,
-                            (uint32_t)(r1 - r0), (uint32_t)m.n_docs, toff.get() + r0, h_off[r0], d_piece[b].get(), st);
-            MMT_HIP(hipMemcpyAsync(h_piece[b].get(), d_piece[b].get(), bytes, hipMemcpyDeviceToHost, st));
-            MMT_HIP(hipStreamSynchronize(st));
-            { std::lock_guard<std::mutex> lk(mu); q.push_back(Job{b, (size_t)bytes}); }
-            cv.notify_all();
-        }
-    } catch (...) {
-        { std::lock_guard<std::mutex> lk(mu); closing = true; }
-        cv.notify_all(); writer.join(); ::close(fd);
-        if (!special) ::unlink(tmp.c_str());
-        throw;
+    for (auto& d : d_piece) d.ensure(longest + 1);
+    PieceWriter writer(longest + 1, 2);
+    writer.open(path, e.device(), false);        // (left open by an exception: its destructor removes PATH.tmp)
+    for (size_t i = 0; i + 1 < cut.size(); i++) {
+        DevBuf<char>& d = d_piece[i & 1];
+        const size_t r0 = cut[i], r1 = cut[i + 1];
+        PieceWriter::Piece pc = writer.room(h_off[r1] - h_off[r0]);
+        mk::table_write(m.d_length.get() + r0, m.d_offsets.get() + r0 * m.n_docs, m.d_strands.get() + r0 * m.n_docs,
+                        (uint32_t)(r1 - r0), (uint32_t)m.n_docs, toff.get() + r0, h_off[r0], d.get(), st);
+        MMT_HIP(hipMemcpyAsync(pc.p, d.get(), pc.n, hipMemcpyDeviceToHost, st));
+        MMT_HIP(hipStreamSynchronize(st));
+        writer.push(pc);
     }
-    { std::lock_guard<std::mutex> lk(mu); closing = true; }
-    cv.notify_all();
-    writer.join();
-    std::string failure;
-    { std::lock_guard<std::mutex> lk(mu); failure = error; }
-    if (::close(fd) != 0 && failure.empty()) failure = "cannot close " + tmp;
-    if (failure.empty() && !special && std::rename(tmp.c_str(), path.c_str()) != 0) failure = "cannot rename " + tmp;
-    if (!failure.empty()) { if (!special) ::unlink(tmp.c_str()); throw std::runtime_error(failure); }
+    writer.close();
 }
 
 void download_merged(Engine& e, MergedRows& m) {

@@ -1,0 +1,83 @@
+// out_file.hpp -- one output file of the library: its name while it is written, the write loop, the error strings.
+// Host code only (extract_mums is built without the device toolchain).
+#pragma once
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <stdexcept>
+#include <string>
+
+namespace mmt {
+
+// digest of a byte stream that arrives in pieces of any size (the text sink's bytes in file order)
+struct StreamDigest {
+    uint64_t h = 0x6d756d656d746f35ull;
+    uint8_t carry[8];
+    uint32_t have = 0;
+    void word(uint64_t w) { h = (h ^ w) * 0x9E3779B97F4A7C15ull; h ^= h >> 29; }
+    void update(const char* p, size_t n) {
+        size_t i = 0;
+        while (have && have < 8 && i < n) carry[have++] = (uint8_t)p[i++];
+        if (have == 8) { uint64_t w; std::memcpy(&w, carry, 8); word(w); have = 0; }
+        for (; i + 8 <= n; i += 8) { uint64_t w; std::memcpy(&w, p + i, 8); word(w); }
+        for (; i < n; i++) carry[have++] = (uint8_t)p[i];
+    }
+    uint64_t final() const { uint64_t x = h; for (uint32_t i = 0; i < have; i++) x = (x ^ carry[i]) * 0x100000001b3ull; return x ^ (x >> 31); }
+};
+
+// The bytes go to PATH.tmp and take the final name in commit(): a run that fails half way -- a short write, a full disk, a
+// consistency check at its end -- must not leave a plausible but truncated PATH.  A path that exists and is not a regular
+// file (a FIFO, /dev/stdout) and "/dev/null" are written as they are; IN_PLACE writes any path under its own name.
+class OutFile {
+public:
+    enum Mode { RENAME, IN_PLACE };
+    OutFile() = default;
+    OutFile(const OutFile&) = delete;
+    ~OutFile() { abort(); }
+    void open(const std::string& path, Mode mode = RENAME) {
+        abort();                    // (a file left open is dropped, PATH.tmp with it)
+        struct stat sb;
+        special_ = path == "/dev/null" || (::stat(path.c_str(), &sb) == 0 && !S_ISREG(sb.st_mode));
+        rename_ = mode == RENAME && !special_;
+        path_ = path; name_ = rename_ ? path + ".tmp" : path; error_.clear();
+        fd_ = ::open(name_.c_str(), special_ ? O_WRONLY : (O_CREAT | O_TRUNC | O_WRONLY), 0644);
+        if (fd_ < 0) throw std::runtime_error("cannot write " + name_);
+    }
+    // false once a write has failed (the first failure stays in error(); later calls write nothing)
+    bool write_all(const void* data, size_t n) {
+        const char* src = static_cast<const char*>(data);
+        for (size_t at = 0; error_.empty() && at < n;) {
+            const ssize_t w = ::write(fd_, src + at, std::min<size_t>(n - at, (size_t)1 << 30));
+            if (w <= 0) error_ = "short write to " + name_;
+            else at += (size_t)w;
+        }
+        return error_.empty();
+    }
+    // closes the file and gives it its name; throws what went wrong since open() after removing PATH.tmp
+    void commit() {
+        if (fd_ >= 0 && ::close(fd_) != 0 && error_.empty()) error_ = "cannot close " + name_;
+        fd_ = -1;
+        if (error_.empty() && rename_ && std::rename(name_.c_str(), path_.c_str()) != 0) error_ = "cannot rename " + name_;
+        if (!error_.empty()) { abort(); throw std::runtime_error(error_); }
+        rename_ = false;
+    }
+    void abort() noexcept {
+        if (fd_ >= 0) ::close(fd_);
+        if (rename_) ::unlink(name_.c_str());
+        fd_ = -1; rename_ = false;
+    }
+    bool special() const { return special_; }       // not a regular file: nobody can read the bytes back
+    const std::string& error() const { return error_; }
+
+private:
+    std::string path_, name_, error_;
+    int fd_ = -1;
+    bool special_ = false, rename_ = false;
+};
+
+}  // namespace mmt
