@@ -43,6 +43,7 @@ static Loaded load(const std::string& path) {
         L.offsets.insert(L.offsets.end(), m.offsets.begin(), m.offsets.end());
         L.strands.insert(L.strands.end(), m.strands.begin(), m.strands.end());
     }
+    if (!L.n_docs) L.n_docs = 1;        // no rows (the reference reads such a file too): the anchor column alone
     return L;
 }
 

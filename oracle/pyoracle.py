@@ -256,14 +256,16 @@ def cli_params(n_docs, k=0, f=1, F=0):
 
 
 def anchor_merge(parts):
-    """parts: list of (length u32[n], offsets i64[n,nd], strands u8[n,nd], nb u16[L0+1])."""
+    """parts: list of (length u32[n], offsets i64[n,nd], strands u8[n,nd], nb u16[L0+1]); n may be 0."""
     L = lib()
     arr = (Partition * len(parts))()
     keep = []
     for i, (length, off, st, nb) in enumerate(parts):
         length = np.ascontiguousarray(length, np.uint32)
-        off = np.ascontiguousarray(off, np.int64).reshape(len(length), -1)
-        st = np.ascontiguousarray(st, np.uint8).reshape(len(length), -1)
+        off, st = np.ascontiguousarray(off, np.int64), np.ascontiguousarray(st, np.uint8)
+        if off.ndim != 2:       # a partition without rows says how many columns it has by its shape (0, nd), or has one
+            off, st = (off.reshape(len(length), -1), st.reshape(len(length), -1)) if len(length) else \
+                (off.reshape(0, 1), st.reshape(0, 1))
         nb = np.ascontiguousarray(nb, np.uint16)
         keep += [length, off, st, nb]
         arr[i] = Partition(len(length), off.shape[1], _p(length).value, _p(off).value, _p(st).value,
