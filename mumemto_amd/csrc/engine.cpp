@@ -463,7 +463,7 @@ void Engine::release_columns(bool keep_anchor_ranks) {
     if (!keep_anchor_ranks) { d_rank_.release(); d_rank64_.release(); anchor_ranks_valid_ = false; }
     d_lcp_.release(); d_plcp_a_.release(); d_long_.release(); d_wpre_.release(); d_wsuf_.release(); d_wide_.release();
     d_cand_.release(); d_flags_.release();
-    for (int k = 0; k < 2; k++) { w_sa_[k].release(); w_hi_[k].release(); w_bwt_[k].release(); w_lcp_[k].release(); }
+    for (WinBufs& w : win_) w.release();
     d_pool_lo_.release(); d_pool_hi_.release(); d_rows_pool_.release(); d_cap_cnt_.release(); d_cap_off_.release();
     lcp_whole_ = false; lcp_col_ready_ = false; columns_kept_ = false;
 }
@@ -547,13 +547,13 @@ void Engine::scan_begin(const mmt_params& p, ScanState& S) {
     range_ev_kind_.clear();
 }
 
-// this rank's share of the closing positions (set_scan_shard): [n k / count, n (k + 1) / count), cut at multiples of 4096
-void Engine::shard_range(uint64_t& lo, uint64_t& hi) const {
+// rank `index`'s share of the closing positions (set_scan_shard): [n k / count, n (k + 1) / count), cut at multiples of 4096
+void Engine::shard_range(uint32_t index, uint64_t& lo, uint64_t& hi) const {
     const uint64_t n = n_, ALIGN_R = 4096;
     lo = 0; hi = n;
     if (shard_count_ <= 1) return;
     auto cut = [&](uint64_t k) { return k >= shard_count_ ? n : (n / shard_count_ * k) / ALIGN_R * ALIGN_R; };
-    lo = cut(shard_index_); hi = cut(shard_index_ + 1);
+    lo = cut(index); hi = cut((uint64_t)index + 1);
 }
 
 // One window: scan kernel, verification, thresholds; rows of a transient window take their suffix-array entries along.
@@ -744,7 +744,7 @@ void Engine::scan(const mmt_params& p) {
     uint64_t shard_lo = 0, shard_hi = n;
     if (shard_count_ > 1) {
         if (preset_ == 2) throw std::runtime_error("a handed-over stream cannot be scanned in shards");
-        shard_range(shard_lo, shard_hi);
+        shard_range(shard_index_, shard_lo, shard_hi);
         range = std::min<uint64_t>(range, std::max<uint64_t>(ALIGN_R, (shard_hi - shard_lo + ALIGN_R - 1) / ALIGN_R * ALIGN_R));
     }
     const bool single = range >= n && shard_count_ == 1;
@@ -783,29 +783,36 @@ void Engine::scan(const mmt_params& p) {
 
 // ---- the window buffers of the producers that emit the columns themselves ----------------------------------------------
 void Engine::window_reserve(int set, uint64_t entries) {
-    w_sa_[set].ensure(entries + 64); w_bwt_[set].ensure(entries + 64); w_lcp_[set].ensure(entries + 64);
-    if (wide_) w_hi_[set].ensure(entries + 64);
-    uint64_t bytes = 0;
-    for (int k = 0; k < 2; k++) bytes += w_sa_[k].bytes() + w_bwt_[k].bytes() + w_lcp_[k].bytes() + w_hi_[k].bytes();
-    window_bytes_peak_ = std::max(window_bytes_peak_, bytes);
+    win_[set].reserve(entries + 64, wide_);
+    window_bytes_peak_ = std::max(window_bytes_peak_, win_[0].bytes() + win_[1].bytes());
 }
 ColWindow Engine::window_view(int set, uint64_t base, uint32_t len, uint32_t first) const {
+    const WinCols c = win_[set].cols(wide_);
     ColWindow w;
-    w.sa.lo = w_sa_[set].get(); w.sa.hi = wide_ ? w_hi_[set].get() : nullptr;
-    w.bwt = w_bwt_[set].get(); w.lcp = w_lcp_[set].get();
+    w.sa.lo = c.sa; w.sa.hi = c.hi; w.bwt = c.bwt; w.lcp = c.lcp;
     w.base = base; w.sa_off = 0; w.len = len; w.first = first; w.more_left = base > 0; w.transient = true;
     return w;
 }
-// keep mode (set_keep_columns): the closing positions of a window also go into whole columns
-void Engine::keep_window(const ColWindow& w) {
-    if (!columns_kept_) return;
-    const uint64_t at = w.base + w.first, cnt = (uint64_t)w.len - w.first;
-    if (!cnt) return;
+// The way of every window a producer emitted into set `set`.  closing_entry: the first entry of the NEXT rank's share closes
+// what is still open at the end of this one's -- its LCP is below the bins' prefix length, below every reportable value: a
+// stand-in entry with LCP 0 behind the window.  Anchor ranks (merge-metadata runs) and keep mode (set_keep_columns: whole
+// columns next to the windows) take the closing positions [w.first, w.len) only, whose values do not depend on how far the
+// window reaches to the left: they follow a scan that succeeded, so that a repeated window leaves them once.
+bool Engine::hand_off_window(ScanState& S, int set, const ColWindow& w, const mmt_params& p, bool closing_entry) {
     hipStream_t st = stream_;
-    MMT_HIP(hipMemcpyAsync(d_sa_.get() + at, w.sa.lo + w.sa_off + w.first, cnt * 4, hipMemcpyDeviceToDevice, st));
-    if (wide_) MMT_HIP(hipMemcpyAsync(d_sa_hi_.get() + at, w.sa.hi + w.sa_off + w.first, cnt, hipMemcpyDeviceToDevice, st));
-    MMT_HIP(hipMemcpyAsync(d_bwt_.get() + at, w.bwt + w.first, cnt, hipMemcpyDeviceToDevice, st));
-    MMT_HIP(hipMemcpyAsync(d_plcp_a_.get() + at, w.lcp + w.first, cnt * 4, hipMemcpyDeviceToDevice, st));
+    const WinCols cols = win_[set].cols(wide_);
+    const uint64_t first_entry = w.base + w.first, count = (uint64_t)w.len - w.first;
+    ColWindow scanned = w;
+    if (closing_entry) { cols.zero_entry(w.len, st); scanned.len = w.len + 1; }
+    if (!scan_window(S, scanned, p)) return false;
+    if (want_anchor_ranks_) {
+        SaCol piece = w.sa; piece.lo += w.first; if (piece.hi) piece.hi += w.first;
+        k::anchor_ranks(piece, first_entry, count, std::min<uint64_t>(doc_len_[0], n_), wide_ ? (void*)d_rank64_.get() : (void*)d_rank_.get(), st);
+    }
+    if (columns_kept_ && count)
+        WinCols::copy(WinCols{d_sa_.get(), wide_ ? d_sa_hi_.get() : nullptr, d_bwt_.get(), d_plcp_a_.get()}, first_entry, cols, w.first, count, st);
+    sink_flush(S);
+    return true;
 }
 
 // ---- A6: rows -> coordinates -> text ---------------------------------------------
@@ -1247,13 +1254,10 @@ void Engine::run(const mmt_params& p) {
     uint32_t auto_p = n_ < (1ull << 30) ? 16 : (uint32_t)std::max<uint64_t>(30, n_ / 1600000000ull + 1);
     // (a modulus that divides the hash of w equal bases ends a phrase at EVERY position of a run of that base -- an assembly gap of
     // megabases becomes megabases of phrases, and the bucket-wise producer cannot slice its bin (guided.cpp): the next modulus)
-    {
-        auto kr = [](uint8_t c, uint32_t w) { uint64_t h = 0; for (uint32_t i = 0; i < w; i++) h = (h * 256 + c) % 1999999973ull; return h; };
-        for (;; auto_p++) {
-            bool bad = false;
-            for (const char c : {'A', 'C', 'G', 'T', 'N'}) bad = bad || kr((uint8_t)c, auto_w) % auto_p == 0;
-            if (!bad) break;
-        }
+    for (;; auto_p++) {
+        bool bad = false;
+        for (const char c : {'A', 'C', 'G', 'T', 'N'}) bad = bad || pk::kr_window_of_run((uint8_t)c, auto_w) % auto_p == 0;
+        if (!bad) break;
     }
     if (kind == 3 || kind == 4) pfp_want_guided_ = true;
     run_slices_ = text_passes_ = batches_ = 0; staged_ = false;
@@ -1295,7 +1299,7 @@ void Engine::run(const mmt_params& p) {
     if (slim) {
         release_sort_scratch();
         d_wpre_.release(); d_wsuf_.release(); d_wide_.release(); d_cand_.release();
-        for (int k = 0; k < 2; k++) { w_sa_[k].release(); w_hi_[k].release(); w_bwt_[k].release(); w_lcp_[k].release(); }
+        for (WinBufs& w : win_) w.release();
         if (one_shot_) pool::shrink_async(device_);      // (the tables of the parse and the windows are gone: rows and outputs remain)
     }
     make_rows(p);

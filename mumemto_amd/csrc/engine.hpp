@@ -47,6 +47,35 @@ struct ColWindow {
     bool more_left = false;   // entry 0 is not the start of the stream (a walk that reaches it is reported)
     bool transient = false;   // the columns are gone after the window: accepted rows keep their suffix-array entries
 };
+// The four columns of a stretch of the stream as one value: suffix array (low words; high bytes when the text is wide), BWT,
+// LCP.  What the window buffers, the tail of a window and the whole columns of keep mode are moved and cleared by.
+struct WinCols {
+    uint32_t* sa = nullptr;
+    uint8_t* hi = nullptr;
+    uint8_t* bwt = nullptr;
+    uint32_t* lcp = nullptr;
+    static void copy(const WinCols& dst, uint64_t dst_at, const WinCols& src, uint64_t src_at, uint64_t count, hipStream_t s) {
+        MMT_HIP(hipMemcpyAsync(dst.sa + dst_at, src.sa + src_at, count * 4, hipMemcpyDeviceToDevice, s));
+        if (dst.hi) MMT_HIP(hipMemcpyAsync(dst.hi + dst_at, src.hi + src_at, count, hipMemcpyDeviceToDevice, s));
+        MMT_HIP(hipMemcpyAsync(dst.bwt + dst_at, src.bwt + src_at, count, hipMemcpyDeviceToDevice, s));
+        MMT_HIP(hipMemcpyAsync(dst.lcp + dst_at, src.lcp + src_at, count * 4, hipMemcpyDeviceToDevice, s));
+    }
+    void zero_entry(uint64_t at, hipStream_t s) const {
+        MMT_HIP(hipMemsetAsync(lcp + at, 0, 4, s));
+        MMT_HIP(hipMemsetAsync(bwt + at, 0, 1, s));
+        MMT_HIP(hipMemsetAsync(sa + at, 0, 4, s));
+        if (hi) MMT_HIP(hipMemsetAsync(hi + at, 0, 1, s));
+    }
+};
+// ... and buffers that own such columns (the high bytes only for a wide text)
+struct WinBufs {
+    DevBuf<uint32_t> sa, lcp;
+    DevBuf<uint8_t> hi, bwt;
+    void reserve(uint64_t entries, bool wide) { sa.ensure(entries); bwt.ensure(entries); lcp.ensure(entries); if (wide) hi.ensure(entries); }
+    void release() { sa.release(); hi.release(); bwt.release(); lcp.release(); }
+    uint64_t bytes() const { return sa.bytes() + bwt.bytes() + lcp.bytes() + hi.bytes(); }
+    WinCols cols(bool wide) const { return WinCols{sa.get(), wide ? hi.get() : nullptr, bwt.get(), lcp.get()}; }
+};
 // what the windows of one run share (Engine::scan_begin / scan_window / scan_end)
 struct ScanState {
     k::ScanArgs a;
@@ -284,8 +313,13 @@ private:
     void scan_end(ScanState& S);
     void window_reserve(int set, uint64_t entries);
     ColWindow window_view(int set, uint64_t base, uint32_t len, uint32_t first) const;
-    void keep_window(const ColWindow& w);
-    void shard_range(uint64_t& lo, uint64_t& hi) const;
+    // A window of set `set` (window_view) from its columns to the rows: [stand-in closing entry] -> scan -> anchor ranks and
+    // keep mode for its closing positions -> sink.  false (nothing of the attempt is kept): scan_window's.
+    bool hand_off_window(ScanState& S, int set, const ColWindow& w, const mmt_params& p, bool closing_entry);
+    void shard_range(uint32_t index, uint64_t& lo, uint64_t& hi) const;
+    // the share of this rank of the bucket-wise producer's stream: bins [bin_lo, bin_hi), pre[b] suffixes in the bins before b
+    struct GuidedShare { std::vector<uint64_t> pre; uint32_t bin_lo = 0, bin_hi = 0; };
+    GuidedShare guided_share(const mmt_params& p);
     EventPair& next_range_event(ScanState& S, int kind);
     void make_rows(const mmt_params& p);
 
@@ -333,8 +367,7 @@ private:
     uint32_t shard_index_ = 0, shard_count_ = 1;
     std::vector<std::pair<uint64_t, uint64_t>> sort_pieces_;
     // the window of the columns that exists (two sets: the bucket-wise producer carries the tail of one into the next)
-    DevBuf<uint32_t> w_sa_[2], w_lcp_[2];
-    DevBuf<uint8_t> w_hi_[2], w_bwt_[2];
+    WinBufs win_[2];
     int keep_columns_ = -1;
     bool columns_kept_ = false, streamed_ = false, pfp_want_guided_ = false;
     // suffix-array entries of the accepted rows (rows of a streamed run index this pool instead of the column)

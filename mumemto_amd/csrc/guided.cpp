@@ -43,13 +43,6 @@ static void mem_mark(int device, const char* what) {
 
 namespace {
 
-// Karp-Rabin hash of a window of w equal bytes (newscan.hpp:84-114: prime 1999999973, base 256)
-uint64_t kr_window_of_run(uint8_t c, uint32_t w) {
-    uint64_t h = 0;
-    for (uint32_t i = 0; i < w; i++) h = (h * 256 + c) % 1999999973ull;
-    return h;
-}
-
 // scratch of one batch (capacity elements)
 struct Batch {
     DevBuf<uint64_t> key_a, key_b, pos_a, pos_b, pos_c;
@@ -213,6 +206,136 @@ RoundStats sort_batch(Batch& X, uint32_t B, const gk::Ctx& ctx, DevBuf<uint8_t>&
     }
     return rs;
 }
+
+// What the batches and windows of a stream loop are made of: a whole bin of leading characters, or a slice of a run bin (the
+// buckets [blo, bhi) of gk::RunSlice; `first`: the bin's first slice).  Of its `count` suffixes `reps` are collected and sorted:
+// all of them in the plain loop, the representatives in the expansion loop.
+struct Piece { uint32_t bin, blo, bhi; uint64_t count, reps; bool slice, first; };
+
+// the symbol a bin's prefix repeats (0: the bin is not a run bin)
+uint32_t run_symbol(const gk::Ctx& ctx, int prefix_chars, uint32_t b) {
+    const uint32_t smask = (1u << ctx.bits) - 1u, sym = b & smask;
+    if (!sym) return 0u;
+    for (int ch = 1; ch < prefix_chars; ch++) if (((b >> (ctx.bits * ch)) & smask) != sym) return 0u;
+    return sym;
+}
+
+// Collects the batches of a stream loop: the suffixes of the pieces [b0, b1), in text order, as the first keys and records of
+// the batch scratch.  Finding them is a pass over the WHOLE text -- count per tile, exclusive sum, fill.  With a staging list
+// (gk::stage_fill) one pass lists the suffixes of as many whole bins as the list holds and every batch takes its own from the
+// list -- count per block of the list, exclusive sum, take; slices of a run bin always come from the text.  A fill or take
+// also counts the range that comes NEXT, so that only the first range of a sequence is counted by a kernel of its own: which
+// range the tile counts and the block counts hold is kept here.  passes(): the passes over the text that filled something.
+class BatchFeeder {
+public:
+    BatchFeeder(const gk::Ctx& ctx, int prefix_chars, const std::vector<Piece>& pieces, const gk::RunSlice& run_tab, uint32_t batch_cap,
+                bool staged, uint64_t stage_cap, DevBuf<uint8_t>& temp, hipStream_t st, const char* who)
+        : ctx_(ctx), pc_(prefix_chars), vb_(pieces), run_tab_(run_tab), cap_(batch_cap), staged_(staged), stage_cap_(stage_cap),
+          n_tiles_((uint32_t)((ctx.n + gk::TILE - 1) / gk::TILE)), temp_(temp), st_(st), who_(who) {
+        tile_cnt_.ensure((size_t)n_tiles_ + 1); tile_off_.ensure((size_t)n_tiles_ + 1);
+        if (staged_) { stage_.ensure(stage_cap + 16); blk_cnt_.ensure(stage_cap / 4096 + 2); blk_off_.ensure(stage_cap / 4096 + 2); blk_tile_.ensure(stage_cap / 4096 + 3); }
+    }
+    // the end b1 of the pieces [b0, b1) before `stop` that go together -- whole bins, or slices of ONE run bin, never both --
+    // with at most `cap` collected suffixes; their suffixes and collected suffixes
+    uint32_t span_end(uint32_t b0, uint32_t stop, uint64_t cap, uint64_t& total, uint64_t& total_rep) const {
+        uint32_t b1 = b0;
+        total = 0; total_rep = 0;
+        while (b1 < stop && vb_[b1].slice == vb_[b0].slice && (!vb_[b0].slice || vb_[b1].bin == vb_[b0].bin) &&
+               total_rep + vb_[b1].reps <= cap && total + vb_[b1].count < (1ull << 40)) { total += vb_[b1].count; total_rep += vb_[b1].reps; b1++; }
+        return b1;
+    }
+    uint32_t next_batch_end(uint32_t b0, uint32_t stop, uint64_t& total, uint64_t& total_rep) const { return span_end(b0, stop, cap_, total, total_rep); }
+    // Staged: when the list does not hold piece b0 (a whole bin) yet, the next pass over the text -- as many whole bins as the
+    // list holds.  Returns where the batch that begins at b0 must stop: the end of the listed pieces, or of all pieces.
+    uint32_t begin_pass_if_needed(uint32_t b0) {
+        const uint32_t nv = (uint32_t)vb_.size();
+        if (!from_list(b0)) return nv;
+        if (b0 < pass_end_) return pass_end_;
+        uint64_t sfx = 0, next_total = 0;
+        pass_end_ = span_end(b0, nv, stage_cap_, sfx, n_staged_);
+        if (pass_end_ == b0) throw std::runtime_error(who_ + ": a bin exceeds the staging list");
+        blocks_ = Counted();                   // (a new list: nothing of it is counted yet)
+        if (!n_staged_) return pass_end_;
+        const Range r = range(b0, pass_end_);
+        // (the pass before counted this pass's suffixes per tile while it filled its own list)
+        if (!tiles_.is(b0, pass_end_)) gk::batch_count(ctx_, pc_, r.lo, r.hi, tile_cnt_.get(), st_);
+        prims::exclusive_sum_u32(temp_, tile_cnt_.get(), tile_off_.get(), n_tiles_, st_);
+        const uint32_t next_end = pass_end_ < nv && !vb_[pass_end_].slice ? span_end(pass_end_, nv, stage_cap_, sfx, next_total) : pass_end_;
+        const bool more = next_total > 0;
+        const Range nx = range(pass_end_, more ? next_end : pass_end_);
+        gk::stage_fill(ctx_, pc_, r.lo, r.hi, tile_off_.get(), stage_.get(), nx.lo, nx.hi, more ? tile_cnt_.get() : nullptr, st_);
+        gk::stage_block_tiles(tile_off_.get(), n_tiles_, n_staged_, blk_tile_.get(), st_);
+        tiles_ = more ? Counted{true, pass_end_, next_end} : Counted();
+        passes_++;
+        return pass_end_;
+    }
+    // the suffixes of the pieces [b0, b1) -- one batch, its end found by next_batch_end -- into X.key_a / X.pos_a
+    void collect(uint32_t b0, uint32_t b1, Batch& X) {
+        const uint32_t nv = (uint32_t)vb_.size();
+        const Range r = range(b0, b1);
+        uint64_t nt = 0, ntr = 0;
+        if (from_list(b0)) {
+            const uint32_t nb = (uint32_t)((n_staged_ + 4095) / 4096);
+            // (the batch before counted this batch's entries per block while it took its own)
+            if (!blocks_.is(b0, b1)) gk::stage_count(stage_.get(), n_staged_, r.lo, r.hi, blk_cnt_.get(), st_);
+            prims::exclusive_sum_u32(temp_, blk_cnt_.get(), blk_off_.get(), nb, st_);
+            const uint32_t nb1 = b1 < pass_end_ ? next_batch_end(b1, pass_end_, nt, ntr) : b1;
+            const bool more = ntr > 0;
+            const Range nx = range(b1, more ? nb1 : b1);
+            gk::stage_take(ctx_, stage_.get(), n_staged_, r.lo, r.hi, blk_off_.get(), X.key_a.get(), X.pos_a.get(), nx.lo, nx.hi,
+                           more ? blk_cnt_.get() : nullptr, tile_off_.get(), blk_tile_.get(), st_);
+            blocks_ = more ? Counted{true, b1, nb1} : Counted();
+            return;
+        }
+        // (the batch before counted this batch's suffixes per tile while it filled its own; a batch of slices counts for itself)
+        if (!tiles_.is(b0, b1)) { gk::batch_count(ctx_, pc_, r.lo, r.hi, tile_cnt_.get(), st_, r.slice); if (r.slice.sym) passes_++; }
+        prims::exclusive_sum_u32(temp_, tile_cnt_.get(), tile_off_.get(), n_tiles_, st_);
+        const uint32_t nb1 = b1 < nv ? next_batch_end(b1, nv, nt, ntr) : b1;
+        const bool more = nt > 0 && !staged_ && !r.slice.sym && !vb_[b1].slice;
+        const Range nx = range(b1, more ? nb1 : b1);
+        gk::batch_fill(ctx_, pc_, r.lo, r.hi, tile_off_.get(), X.key_a.get(), X.pos_a.get(), nx.lo, nx.hi, more ? tile_cnt_.get() : nullptr,
+                       st_, r.slice);
+        tiles_ = more ? Counted{true, b1, nb1} : Counted();
+        passes_++;
+        if (vb_[b0].slice) pass_end_ = b1;     // (the list, if any, holds nothing the next whole bin could take)
+    }
+    int passes() const { return passes_; }
+
+private:
+    // which pieces a table of counts holds, if any
+    struct Counted {
+        bool any = false;
+        uint32_t lo = 0, hi = 0;
+        bool is(uint32_t a, uint32_t b) const { return any && lo == a && hi == b; }
+    };
+    // the kernels' view of the pieces [b0, b1): a range of real bins + the buckets of a run bin's slices
+    struct Range { uint32_t lo = 0, hi = 0; gk::RunSlice slice; };
+    Range range(uint32_t b0, uint32_t b1) const {
+        Range r;
+        if (b0 >= b1) return r;
+        r.lo = vb_[b0].bin; r.hi = vb_[b1 - 1].bin + 1;
+        if (vb_[b0].slice) { r.slice = run_tab_; r.slice.sym = run_symbol(ctx_, pc_, vb_[b0].bin); r.slice.blo = vb_[b0].blo; r.slice.bhi = vb_[b1 - 1].bhi; }
+        return r;
+    }
+    bool from_list(uint32_t b0) const { return staged_ && !vb_[b0].slice; }
+
+    const gk::Ctx& ctx_;
+    const int pc_;
+    const std::vector<Piece>& vb_;
+    const gk::RunSlice run_tab_;               // the tables of the tiles (sym, blo, bhi are set per range)
+    const uint64_t cap_;
+    const bool staged_;
+    const uint64_t stage_cap_;
+    const uint32_t n_tiles_;
+    DevBuf<uint8_t>& temp_;
+    hipStream_t st_;
+    const std::string who_;
+    DevBuf<uint32_t> tile_cnt_, tile_off_, stage_, blk_cnt_, blk_off_, blk_tile_;
+    Counted tiles_, blocks_;                   // tile_cnt_ / blk_cnt_ hold the counts of these pieces
+    uint32_t pass_end_ = 0;                    // staged: the whole-bin pieces [.., pass_end_) are in the list, n_staged_ entries
+    uint64_t n_staged_ = 0;
+    int passes_ = 0;
+};
 
 }  // namespace
 
@@ -638,11 +761,40 @@ void Engine::guided_check_errors(const char* what) {
                                  " neighbours equal up to the end of alpha without ascending parse ranks)");
 }
 
+// The shares of the ranks of the bucket-wise producer's stream: whole bins.  Rank k takes the bins from the first one whose
+// cumulative count of TEXT suffixes reaches k n / count (every rank derives the same shares from the same histogram, for the
+// plain and the expansion loop alike: sort_pieces_); nothing is exchanged but the rows.
+Engine::GuidedShare Engine::guided_share(const mmt_params& p) {
+    PfpState& S = *pfp_;
+    const uint64_t n = n_;
+    const uint32_t n_bins = S.g_nbins;
+    if (p.min_match_len < (uint32_t)S.g_prefix)
+        throw std::runtime_error("guided producer: the bins were formed for another minimum match length");
+    GuidedShare sh;
+    std::vector<uint64_t>& pre = sh.pre;                       // suffixes in the bins before bin b
+    pre.assign((size_t)n_bins + 1, 0);
+    for (uint32_t bq = 0; bq < n_bins; bq++) pre[bq + 1] = pre[bq] + S.g_bins[bq];
+    if (pre[n_bins] != n) throw std::runtime_error("guided sort: the histogram of leading characters does not cover the text");
+    std::vector<uint32_t> cut(shard_count_ + 1, 0);
+    cut[shard_count_] = n_bins;
+    for (uint32_t k = 1; k < shard_count_; k++) {
+        const uint64_t target = (uint64_t)((unsigned __int128)n * k / shard_count_);
+        cut[k] = std::max<uint32_t>(cut[k - 1], (uint32_t)(std::lower_bound(pre.begin(), pre.end(), target) - pre.begin()));
+        if (cut[k] > n_bins) cut[k] = n_bins;
+    }
+    sort_pieces_.clear();
+    for (uint32_t q = 0; q < shard_count_; q++) sort_pieces_.emplace_back(pre[cut[q]], pre[cut[q + 1]] - pre[cut[q]]);
+    sh.bin_lo = cut[shard_index_]; sh.bin_hi = cut[shard_index_ + 1];
+    S.g_share_lo = sh.bin_lo; S.g_share_hi = sh.bin_hi; S.g_share_valid = true;
+    if (shard_count_ > 1 && p.merge_metadata)
+        throw std::runtime_error("merge metadata needs the whole stream on one rank (partition the documents instead)");
+    return sh;
+}
+
 // The stream, batch by batch.  A batch = whole bins of leading characters = one contiguous piece of the suffix array: its
 // suffixes are collected in text order, sorted, written as a window of the columns (suffix array, BWT, LCP from the
 // parse), scanned, and dropped; the accepted rows take their suffix-array entries along.  A rank of a sharded run takes
-// the bins from the first one whose cumulative count reaches k n / count (every rank derives the same shares from the
-// same histogram); nothing is exchanged but the rows.
+// its share of the bins (guided_share).
 void Engine::guided_stream(ScanState& SS, const mmt_params& p) {
     PfpState& S = *pfp_;
     const uint64_t n = n_;
@@ -669,31 +821,13 @@ void Engine::guided_stream(ScanState& SS, const mmt_params& p) {
     if (pfp_->expand) { guided_stream_expand(SS, p); print_prof(); return; }
     const gk::Ctx& ctx = S.gctx;
     const int prefix_chars = S.g_prefix;
-    const uint32_t n_bins = S.g_nbins;
     const std::vector<uint64_t>& bins = S.g_bins;
     const bool stats = std::getenv("MMT_GUIDED_STATS") != nullptr;
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto t0 = now();
-    if (p.min_match_len < (uint32_t)prefix_chars)
-        throw std::runtime_error("guided producer: the bins were formed for another minimum match length");
-
-    // ---- shares of the ranks: whole bins ----
-    std::vector<uint64_t> pre(n_bins + 1, 0);                  // suffixes in the bins before bin b
-    for (uint32_t bq = 0; bq < n_bins; bq++) pre[bq + 1] = pre[bq] + bins[bq];
-    if (pre[n_bins] != n) throw std::runtime_error("guided sort: the histogram of leading characters does not cover the text");
-    std::vector<uint32_t> cut(shard_count_ + 1, 0);
-    cut[shard_count_] = n_bins;
-    for (uint32_t k = 1; k < shard_count_; k++) {
-        const uint64_t target = (uint64_t)((unsigned __int128)n * k / shard_count_);
-        cut[k] = std::max<uint32_t>(cut[k - 1], (uint32_t)(std::lower_bound(pre.begin(), pre.end(), target) - pre.begin()));
-        if (cut[k] > n_bins) cut[k] = n_bins;
-    }
-    sort_pieces_.clear();
-    for (uint32_t q = 0; q < shard_count_; q++) sort_pieces_.emplace_back(pre[cut[q]], pre[cut[q + 1]] - pre[cut[q]]);
-    const uint32_t bin_lo = cut[shard_index_], bin_hi = cut[shard_index_ + 1];
-    S.g_share_lo = bin_lo; S.g_share_hi = bin_hi; S.g_share_valid = true;
-    if (shard_count_ > 1 && p.merge_metadata)
-        throw std::runtime_error("merge metadata needs the whole stream on one rank (partition the documents instead)");
+    const GuidedShare sh = guided_share(p);
+    const std::vector<uint64_t>& pre = sh.pre;
+    const uint32_t bin_lo = sh.bin_lo, bin_hi = sh.bin_hi;
 
     // ---- batch capacity: the batch scratch + two window sets (a batch with the tail of the one before) ----
     // what a batch's first closing position may need of the batch before: the last bin of that batch, as far as an
@@ -747,17 +881,14 @@ void Engine::guided_stream(ScanState& SS, const mmt_params& p) {
     }
     Batch X;
     X.reserve((uint32_t)cap64);
-    DevBuf<uint32_t> stage, blk_tile;
-    DevBuf<uint32_t> blk_cnt, blk_off;
-    if (staged) { stage.ensure(stage_cap + 16); blk_cnt.ensure(stage_cap / 4096 + 2); blk_off.ensure(stage_cap / 4096 + 2); blk_tile.ensure(stage_cap / 4096 + 3); }
+    std::vector<Piece> vb;                     // every bin of the share a whole piece, all its suffixes collected
+    for (uint32_t b = bin_lo; b < bin_hi; b++) vb.push_back(Piece{b, 0, 0, bins[b], bins[b], false, true});
+    const uint32_t nv = (uint32_t)vb.size();
     window_reserve(0, head_room + cap64 + 16);
     window_reserve(1, head_room + cap64 + 16);
     DevBuf<uint64_t> carry;
     carry.ensure(2);
-    const uint32_t n_tiles = (uint32_t)((n + gk::TILE - 1) / gk::TILE);
-    DevBuf<uint32_t> tile_cnt, tile_off;
-    tile_cnt.ensure((size_t)n_tiles + 1); tile_off.ensure((size_t)n_tiles + 1);
-    const uint64_t anchor = std::min<uint64_t>(doc_len_[0], n);
+    BatchFeeder feed(ctx, prefix_chars, vb, gk::RunSlice(), X.cap, staged, stage_cap, d_temp_, st, "guided sort");
 
     uint64_t base = pre[bin_lo], active_sum = 0, small_sum = 0;
     const uint64_t piece_end = pre[bin_hi];
@@ -765,109 +896,38 @@ void Engine::guided_stream(ScanState& SS, const mmt_params& p) {
     uint64_t prev_len = 0;                 // entries of the window before (without a virtual closing entry)
     uint32_t prev_last_bin = 0;            // its last non-empty bin
     bool have_prev = false;
-    uint32_t pass_end = bin_lo;            // staged: the bins [.., pass_end) are in the list
-    uint32_t counted_lo = 0, counted_hi = 0;   // ... and tile_cnt holds the per-tile counts of the bins [counted_lo, counted_hi)
-    uint32_t taken_lo = 0, taken_hi = 0;       // ... and blk_cnt the per-block counts of the list's entries of the bins [taken_lo, taken_hi)
-    uint64_t n_staged = 0;
-    int passes = 0;
-    for (uint32_t b0 = bin_lo; b0 < bin_hi;) {
-        if (staged && b0 == pass_end) {    // the next pass over the text: as many bins as the list holds
-            n_staged = 0;
-            while (pass_end < bin_hi && n_staged + bins[pass_end] <= stage_cap) n_staged += bins[pass_end++];
-            if (pass_end == b0) throw std::runtime_error("guided sort: a bin exceeds the staging list");
-            taken_lo = taken_hi = 0;               // (a new list: nothing of it is counted yet)
-            if (n_staged) {
-                // (the pass before counted this pass's suffixes per tile while it filled its own list)
-                if (!(counted_lo == b0 && counted_hi == pass_end)) gk::batch_count(ctx, prefix_chars, b0, pass_end, tile_cnt.get(), st);
-                prims::exclusive_sum_u32(d_temp_, tile_cnt.get(), tile_off.get(), n_tiles, st);
-                uint32_t next_end = pass_end;
-                uint64_t next_total = 0;
-                while (next_end < bin_hi && next_total + bins[next_end] <= stage_cap) next_total += bins[next_end++];
-                const bool more = next_total > 0;
-                gk::stage_fill(ctx, prefix_chars, b0, pass_end, tile_off.get(), stage.get(), pass_end, next_end,
-                               more ? tile_cnt.get() : nullptr, st);
-                gk::stage_block_tiles(tile_off.get(), n_tiles, n_staged, blk_tile.get(), st);
-                counted_lo = more ? pass_end : 0; counted_hi = more ? next_end : 0;
-            }
-            passes++;
-        }
-        uint64_t total = 0;
-        uint32_t b1 = b0;
-        const uint32_t b_stop = staged ? pass_end : bin_hi;
-        while (b1 < b_stop && total + bins[b1] <= X.cap) total += bins[b1++];
+    for (uint32_t b0 = 0; b0 < nv;) {
+        uint64_t total = 0, total_rep = 0;
+        const uint32_t b1 = feed.next_batch_end(b0, feed.begin_pass_if_needed(b0), total, total_rep);
         if (b1 == b0) throw std::runtime_error("guided sort: a bin exceeds the batch");
         if (total) {
             const uint32_t B = (uint32_t)total;
             const int set = batches & 1;
+            const WinCols win = win_[set].cols(wide_);
             EventPair& ee = next_range_event(SS, 3);
             ee.start(st);
-            if (staged) {
-                const uint32_t nb = (uint32_t)((n_staged + 4095) / 4096);
-                // (the batch before counted this batch's entries per block while it took its own)
-                if (!(taken_lo == b0 && taken_hi == b1)) gk::stage_count(stage.get(), n_staged, b0, b1, blk_cnt.get(), st);
-                prims::exclusive_sum_u32(d_temp_, blk_cnt.get(), blk_off.get(), nb, st);
-                uint32_t nb1 = b1;
-                uint64_t next_total = 0;
-                while (nb1 < pass_end && next_total + bins[nb1] <= X.cap) next_total += bins[nb1++];
-                const bool more = next_total > 0;
-                gk::stage_take(ctx, stage.get(), n_staged, b0, b1, blk_off.get(), X.key_a.get(), X.pos_a.get(), b1, nb1,
-                               more ? blk_cnt.get() : nullptr, tile_off.get(), blk_tile.get(), st);
-                taken_lo = more ? b1 : 0; taken_hi = more ? nb1 : 0;
-            } else {
-                // (the batch before counted this batch's suffixes per tile while it filled its own)
-                if (!(counted_lo == b0 && counted_hi == b1)) gk::batch_count(ctx, prefix_chars, b0, b1, tile_cnt.get(), st);
-                prims::exclusive_sum_u32(d_temp_, tile_cnt.get(), tile_off.get(), n_tiles, st);
-                uint32_t nb1 = b1;
-                uint64_t next_total = 0;
-                while (nb1 < bin_hi && next_total + bins[nb1] <= X.cap) next_total += bins[nb1++];
-                const bool more = next_total > 0;
-                gk::batch_fill(ctx, prefix_chars, b0, b1, tile_off.get(), X.key_a.get(), X.pos_a.get(), b1, nb1,
-                               more ? tile_cnt.get() : nullptr, st);
-                counted_lo = more ? b1 : 0; counted_hi = more ? nb1 : 0;
-            }
+            feed.collect(b0, b1, X);
             // (the LCP values the sort finds on its way go straight into the window, behind the tail of the batch before)
             uint64_t ext = 0;
             if (have_prev) ext = std::min<uint64_t>(std::min<uint64_t>(bins[prev_last_bin], prev_len), capped ? SS.ext0 : ~0ull);
             if (ext > head_room) throw std::runtime_error("guided sort: window head room too small");
             const RmqView rmq = S.plcp.view();
-            RoundStats rs = sort_batch(X, B, ctx, d_temp_, S.err.get(), st, w_lcp_[set].get() + ext, &rmq);
+            RoundStats rs = sort_batch(X, B, ctx, d_temp_, S.err.get(), st, win.lcp + ext, &rmq);
             // the window: [tail of the batch before | this batch | one virtual closing entry at the end of a rank's share]
-            if (ext) {
-                const int o = set ^ 1;
-                const uint64_t from = prev_len - ext;
-                MMT_HIP(hipMemcpyAsync(w_sa_[set].get(), w_sa_[o].get() + from, ext * 4, hipMemcpyDeviceToDevice, st));
-                if (wide_) MMT_HIP(hipMemcpyAsync(w_hi_[set].get(), w_hi_[o].get() + from, ext, hipMemcpyDeviceToDevice, st));
-                MMT_HIP(hipMemcpyAsync(w_bwt_[set].get(), w_bwt_[o].get() + from, ext, hipMemcpyDeviceToDevice, st));
-                MMT_HIP(hipMemcpyAsync(w_lcp_[set].get(), w_lcp_[o].get() + from, ext * 4, hipMemcpyDeviceToDevice, st));
-            }
-            SaCol wsa; wsa.lo = w_sa_[set].get(); wsa.hi = wide_ ? w_hi_[set].get() : nullptr;
-            gk::write_columns(ctx, X.pos_b.get(), B, ext, wsa, w_bwt_[set].get(), st);
-            gk::batch_lcp(ctx, S.plcp.view(), X.pos_b.get(), B, carry.get(), have_prev, w_lcp_[set].get() + ext, S.err.get(), st);
+            if (ext) WinCols::copy(win, 0, win_[set ^ 1].cols(wide_), prev_len - ext, ext, st);
+            SaCol wsa; wsa.lo = win.sa; wsa.hi = win.hi;
+            gk::write_columns(ctx, X.pos_b.get(), B, ext, wsa, win.bwt, st);
+            gk::batch_lcp(ctx, S.plcp.view(), X.pos_b.get(), B, carry.get(), have_prev, win.lcp + ext, S.err.get(), st);
             MMT_HIP(hipMemcpyAsync(carry.get(), X.pos_b.get() + (B - 1), 8, hipMemcpyDeviceToDevice, st));
             ee.stop(st);
             stream_entries_ += B;
-            uint64_t len = ext + B;
+            const uint64_t len = ext + B;
             ColWindow w = window_view(set, base - ext, (uint32_t)len, (uint32_t)ext);
             w.more_left = false;          // nothing an interval of this window could reach lies further left (bins)
-            keep_window(w);
-            if (want_anchor_ranks_) {
-                SaCol piece = w.sa; piece.lo += ext; if (piece.hi) piece.hi += ext;
-                k::anchor_ranks(piece, base, B, anchor, wide_ ? (void*)d_rank64_.get() : (void*)d_rank_.get(), st);
-            }
-            const bool last_of_share = b1 == bin_hi || base + B == piece_end;
-            if (last_of_share && base + B < n) {
-                // the first entry of the next rank's share closes what is still open here: its LCP is below the bins'
-                // prefix length, below every reportable value -- stand-in entry with LCP 0
-                MMT_HIP(hipMemsetAsync(w_lcp_[set].get() + len, 0, 4, st));
-                MMT_HIP(hipMemsetAsync(w_bwt_[set].get() + len, 0, 1, st));
-                MMT_HIP(hipMemsetAsync(w_sa_[set].get() + len, 0, 4, st));
-                if (wide_) MMT_HIP(hipMemsetAsync(w_hi_[set].get() + len, 0, 1, st));
-                w.len = (uint32_t)(len + 1);
-            }
-            if (!scan_window(SS, w, p)) throw std::runtime_error("guided sort: a walk left its bin");
-            sink_flush(SS);
+            const bool last_of_share = b1 == nv || base + B == piece_end;
+            if (!hand_off_window(SS, set, w, p, last_of_share && base + B < n)) throw std::runtime_error("guided sort: a walk left its bin");
             prev_len = len; have_prev = true;
-            for (uint32_t b = b1; b-- > b0;) if (bins[b]) { prev_last_bin = b; break; }
+            for (uint32_t b = b1; b-- > b0;) if (vb[b].count) { prev_last_bin = vb[b].bin; break; }
             base += B; batches++; rounds_max = std::max(rounds_max, rs.rounds); active_sum += rs.active_sum; small_sum += rs.small;
         }
         b0 = b1;
@@ -876,10 +936,10 @@ void Engine::guided_stream(ScanState& SS, const mmt_params& p) {
     print_prof();
     if (base != piece_end) throw std::runtime_error("guided sort: the batches do not cover the text exactly once");
     S.rounds_dict = rounds_max; S.emit_launches = (uint32_t)batches;
-    run_slices_ = 0; text_passes_ = (uint32_t)(staged ? passes : batches); batches_ = (uint32_t)batches; staged_ = staged;
+    run_slices_ = 0; text_passes_ = (uint32_t)feed.passes(); batches_ = (uint32_t)batches; staged_ = staged;
     MMT_HIP(hipStreamSynchronize(st));
     const double ms = std::chrono::duration<double, std::milli>(now() - t0).count();
-    if (stats && staged) std::fprintf(stderr, "[guided] %d passes over the text for those batches (a list of %llu suffixes)\n", passes,
+    if (stats && staged) std::fprintf(stderr, "[guided] %d passes over the text for those batches (a list of %llu suffixes)\n", feed.passes(),
                                       (unsigned long long)stage_cap);
     if (stats) std::fprintf(stderr, "[guided] %llu suffixes in %d batches of at most %u: %.1f ms with their scans; %.3f of them settled in "
                             "small groups by comparison, %.3f element-rounds per suffix in %d rounds at most\n",
@@ -911,28 +971,13 @@ void Engine::guided_stream_expand(ScanState& SS, const mmt_params& p) {
     const bool stats = std::getenv("MMT_GUIDED_STATS") != nullptr;
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto t0 = now();
-    if (p.min_match_len < (uint32_t)prefix_chars)
-        throw std::runtime_error("guided producer: the bins were formed for another minimum match length");
     if (!S.ptab.get() || (!S.occ.get() && !S.occ12.get())) throw std::runtime_error("expansion: the inverted lists are gone");
-
-    // ---- shares of the ranks: whole bins, cut by the TEXT suffixes (the same shares as the plain producer's) ----
-    std::vector<uint64_t> pre(n_bins + 1, 0);
+    // (the shares are cut by the TEXT suffixes: the same as the plain loop's)
+    const GuidedShare sh = guided_share(p);
+    const std::vector<uint64_t>& pre = sh.pre;
+    const uint32_t bin_lo = sh.bin_lo, bin_hi = sh.bin_hi;
     uint64_t reps_total = 0;
-    for (uint32_t bq = 0; bq < n_bins; bq++) { pre[bq + 1] = pre[bq] + bins[bq]; reps_total += rbins[bq]; }
-    if (pre[n_bins] != n) throw std::runtime_error("guided sort: the histogram of leading characters does not cover the text");
-    std::vector<uint32_t> cut(shard_count_ + 1, 0);
-    cut[shard_count_] = n_bins;
-    for (uint32_t k = 1; k < shard_count_; k++) {
-        const uint64_t target = (uint64_t)((unsigned __int128)n * k / shard_count_);
-        cut[k] = std::max<uint32_t>(cut[k - 1], (uint32_t)(std::lower_bound(pre.begin(), pre.end(), target) - pre.begin()));
-        if (cut[k] > n_bins) cut[k] = n_bins;
-    }
-    sort_pieces_.clear();
-    for (uint32_t q = 0; q < shard_count_; q++) sort_pieces_.emplace_back(pre[cut[q]], pre[cut[q + 1]] - pre[cut[q]]);
-    const uint32_t bin_lo = cut[shard_index_], bin_hi = cut[shard_index_ + 1];
-    S.g_share_lo = bin_lo; S.g_share_hi = bin_hi; S.g_share_valid = true;
-    if (shard_count_ > 1 && p.merge_metadata)
-        throw std::runtime_error("merge metadata needs the whole stream on one rank (partition the documents instead)");
+    for (uint32_t bq = 0; bq < n_bins; bq++) reps_total += rbins[bq];
 
     // ---- capacities.  A BATCH is what is collected by one pass over the text and sorted at once: representatives of whole
     // bins, at most 2^30; the emitter's entry and group tables of the batch live in the sort's scratch, which is dead by then.
@@ -943,13 +988,6 @@ void Engine::guided_stream_expand(ScanState& SS, const mmt_params& p) {
     // whole genomes with 60 Mbp of gaps each -- is not cut by more leading characters, but its order is known in closed form
     // (guided_kernels.hip RunSlice): when it exceeds a batch or a window it is produced in slices.  Only in the capped modes: an
     // interval of an uncapped mode may be as long as its bin, and a window must hold it.  (MMT_GUIDED_SLICE=<suffixes>: tests)
-    const uint32_t smask = (1u << ctx.bits) - 1u;
-    auto run_symbol = [&](uint32_t b) -> uint32_t {
-        const uint32_t sym = b & smask;
-        if (!sym) return 0u;
-        for (int ch = 1; ch < prefix_chars; ch++) if (((b >> (ctx.bits * ch)) & smask) != sym) return 0u;
-        return sym;
-    };
     const uint64_t slice_env = std::getenv("MMT_GUIDED_SLICE") ? std::strtoull(std::getenv("MMT_GUIDED_SLICE"), nullptr, 10) : 0;
     // (the closed form needs every phrase suffix that begins inside a run to reach beyond the run's end -- all occurrences of a
     // representative then share (r, X0).  That holds unless the window of w equal symbols is itself a trigger of the parse
@@ -957,12 +995,12 @@ void Engine::guided_stream_expand(ScanState& SS, const mmt_params& p) {
     // parameters avoid such moduli (engine.cpp), a parse that was asked for with one keeps its bins whole)
     auto run_triggers = [&](uint32_t sym) {
         for (int c = 0; c < 256; c++)
-            if (S.g_code[c] == sym) return kr_window_of_run((uint8_t)c, S.w) % S.p == 0;
+            if (S.g_code[c] == sym) return pk::kr_window_of_run((uint8_t)c, S.w) % S.p == 0;
         return true;
     };
     std::vector<char> keep_whole(n_bins, 0);        // run bins whose slices would not fit a batch either: produced as whole bins
     auto sliceable = [&](uint32_t b) {
-        const uint32_t sym = run_symbol(b);
+        const uint32_t sym = run_symbol(ctx, prefix_chars, b);
         return capped && sym != 0 && !keep_whole[b] && !run_triggers(sym) && !std::getenv("MMT_GUIDED_NO_SLICES");
     };
     uint64_t largest = 0, largest_rep = 0, share = 0, share_rep = 0, largest_any = 0;
@@ -986,7 +1024,6 @@ void Engine::guided_stream_expand(ScanState& SS, const mmt_params& p) {
     const uint64_t WIN_MAX = 1ull << 31;                                           // (a window and its tail stay well below 2^32 entries)
     uint64_t win_cap = 0, rep_cap = 0, stage_cap = 0;
     bool staged = false;
-    struct Piece { uint32_t bin, blo, bhi; uint64_t count, reps; bool slice, first; };
     std::vector<Piece> vb;
     DevBuf<uint64_t> run_lead;
     DevBuf<uint8_t> run_first, run_follow;
@@ -1076,7 +1113,7 @@ void Engine::guided_stream_expand(ScanState& SS, const mmt_params& p) {
             d_hist.ensure(2 * (size_t)NB);
             MMT_HIP(hipMemsetAsync(d_hist.get(), 0, 2 * (size_t)NB * 8, st));
             gk::RunSlice rs = run_tab;
-            rs.sym = run_symbol(b);
+            rs.sym = run_symbol(ctx, prefix_chars, b);
             gk::run_hist(ctx, prefix_chars, b, rs, d_hist.get(), st);
             std::vector<uint64_t> h;
             d2h(h, d_hist.get(), 2 * (size_t)NB, st);
@@ -1145,18 +1182,12 @@ void Engine::guided_stream_expand(ScanState& SS, const mmt_params& p) {
     S.sege.ensure(C + 2); S.fb_group.ensure(C + 2);
     window_reserve(0, head_room + win_cap + 16);
     // the tail of the window before (its last `head_room` entries at most)
-    DevBuf<uint32_t> t_sa, t_lcp;
-    DevBuf<uint8_t> t_hi, t_bwt;
-    t_sa.ensure(head_room + 16); t_lcp.ensure(head_room + 16); t_bwt.ensure(head_room + 16);
-    if (W) t_hi.ensure(head_room + 16);
+    WinBufs tail_bufs;
+    tail_bufs.reserve(head_room + 16, W);
+    const WinCols win = win_[0].cols(W), tail = tail_bufs.cols(W);
     DevBuf<uint64_t> carry;
     carry.ensure(2);
-    DevBuf<uint32_t> tile_cnt, tile_off;
-    tile_cnt.ensure((size_t)n_tiles + 1); tile_off.ensure((size_t)n_tiles + 1);
-    DevBuf<uint32_t> stage, blk_tile;
-    DevBuf<uint32_t> blk_cnt, blk_off;
-    if (staged) { stage.ensure(stage_cap + 16); blk_cnt.ensure(stage_cap / 4096 + 2); blk_off.ensure(stage_cap / 4096 + 2); blk_tile.ensure(stage_cap / 4096 + 3); }
-    const uint64_t anchor = std::min<uint64_t>(doc_len_[0], n);
+    BatchFeeder feed(ctx, prefix_chars, vb, run_tab, X.cap, staged, stage_cap, d_temp_, st, "guided sort (expansion)");
     const RmqView rmq = S.plcp.view();
     S.emit_ready = true;
 
@@ -1170,88 +1201,17 @@ void Engine::guided_stream_expand(ScanState& SS, const mmt_params& p) {
     uint64_t tail_len = 0;
     uint32_t prev_last_bin = 0;
     bool have_prev = false;
-    uint32_t counted_lo = 0, counted_hi = 0;
     double ms_sort = 0, ms_emit = 0;
-    // (pieces [b0, b1): whole bins, or slices of ONE run bin -- never both in a batch; `stop`: the end of the staged pieces)
-    auto next_batch_end = [&](uint32_t b0, uint32_t stop, uint64_t& total, uint64_t& total_rep) {
-        uint32_t b1 = b0;
-        total = 0; total_rep = 0;
-        while (b1 < stop && vb[b1].slice == vb[b0].slice && (!vb[b0].slice || vb[b1].bin == vb[b0].bin) &&
-               total_rep + vb[b1].reps <= X.cap && total + vb[b1].count < (1ull << 40)) { total += vb[b1].count; total_rep += vb[b1].reps; b1++; }
-        return b1;
-    };
-    // the kernels' view of pieces [b0, b1): a range of real bins + the range of buckets of a run bin's slices
-    auto real_range = [&](uint32_t b0, uint32_t b1, uint32_t& lo, uint32_t& hi, gk::RunSlice& out) {
-        lo = hi = 0; out = gk::RunSlice();
-        if (b0 >= b1) return;
-        lo = vb[b0].bin; hi = vb[b1 - 1].bin + 1;
-        if (vb[b0].slice) { out = run_tab; out.sym = run_symbol(vb[b0].bin); out.blo = vb[b0].blo; out.bhi = vb[b1 - 1].bhi; }
-    };
-    uint32_t pass_end = 0;                     // staged: the whole-bin pieces [.., pass_end) are in the list
-    uint32_t taken_lo = 0, taken_hi = 0;       // ... and blk_cnt holds the per-block counts of the list's entries of the pieces [taken_lo - 1, taken_hi - 1)
-    uint64_t n_staged = 0;
-    int passes = 0;
     for (uint32_t b0 = 0; b0 < nv;) {
-        const bool from_list = staged && !vb[b0].slice;
-        if (from_list && b0 >= pass_end) {     // the next pass over the text: as many whole bins as the list holds
-            pass_end = b0; n_staged = 0;
-            while (pass_end < nv && !vb[pass_end].slice && n_staged + vb[pass_end].reps <= stage_cap) n_staged += vb[pass_end++].reps;
-            if (pass_end == b0) throw std::runtime_error("guided sort (expansion): a bin exceeds the staging list");
-            taken_lo = taken_hi = 0;
-            if (n_staged) {
-                uint32_t lo, hi, nlo, nhi;
-                gk::RunSlice none;
-                real_range(b0, pass_end, lo, hi, none);
-                if (!(counted_lo == b0 + 1 && counted_hi == pass_end + 1)) gk::batch_count(ctx, prefix_chars, lo, hi, tile_cnt.get(), st);
-                prims::exclusive_sum_u32(d_temp_, tile_cnt.get(), tile_off.get(), n_tiles, st);
-                uint32_t next_end = pass_end;
-                uint64_t next_total = 0;
-                while (next_end < nv && !vb[next_end].slice && next_total + vb[next_end].reps <= stage_cap) next_total += vb[next_end++].reps;
-                const bool more = next_total > 0;
-                real_range(pass_end, next_end, nlo, nhi, none);
-                gk::stage_fill(ctx, prefix_chars, lo, hi, tile_off.get(), stage.get(), nlo, more ? nhi : nlo, more ? tile_cnt.get() : nullptr, st);
-                gk::stage_block_tiles(tile_off.get(), n_tiles, n_staged, blk_tile.get(), st);
-                counted_lo = more ? pass_end + 1 : 0; counted_hi = more ? next_end + 1 : 0;
-                passes++;
-            }
-        }
         uint64_t total = 0, total_rep = 0;
-        const uint32_t b_stop = from_list ? pass_end : nv;
-        const uint32_t b1 = next_batch_end(b0, b_stop, total, total_rep);
+        const uint32_t b1 = feed.next_batch_end(b0, feed.begin_pass_if_needed(b0), total, total_rep);
         if (b1 == b0) throw std::runtime_error("guided sort (expansion): a bin exceeds the batch");
         if (total && !total_rep) throw std::runtime_error("guided sort (expansion): suffixes without a representative");
         if (!total) { b0 = b1; continue; }
         const uint32_t B = (uint32_t)total_rep;
         auto t_a = now();
         // ---- collect and sort the representatives of the pieces [b0, b1) ----
-        uint32_t r_lo, r_hi, nr_lo, nr_hi;
-        gk::RunSlice rsl, nrs;
-        real_range(b0, b1, r_lo, r_hi, rsl);
-        uint64_t nt = 0, ntr = 0;
-        if (from_list) {
-            const uint32_t nb = (uint32_t)((n_staged + 4095) / 4096);
-            // (the batch before counted this batch's entries per block while it took its own)
-            if (!(taken_lo == b0 + 1 && taken_hi == b1 + 1)) gk::stage_count(stage.get(), n_staged, r_lo, r_hi, blk_cnt.get(), st);
-            prims::exclusive_sum_u32(d_temp_, blk_cnt.get(), blk_off.get(), nb, st);
-            const uint32_t nb1 = b1 < pass_end ? next_batch_end(b1, pass_end, nt, ntr) : b1;
-            real_range(b1, nb1, nr_lo, nr_hi, nrs);
-            const bool more = ntr > 0;
-            gk::stage_take(ctx, stage.get(), n_staged, r_lo, r_hi, blk_off.get(), X.key_a.get(), X.pos_a.get(), nr_lo, more ? nr_hi : nr_lo,
-                           more ? blk_cnt.get() : nullptr, tile_off.get(), blk_tile.get(), st);
-            taken_lo = more ? b1 + 1 : 0; taken_hi = more ? nb1 + 1 : 0;
-        } else {
-            // (the batch before counted this batch's representatives per tile while it collected its own)
-            if (!(counted_lo == b0 + 1 && counted_hi == b1 + 1)) { gk::batch_count(ctx, prefix_chars, r_lo, r_hi, tile_cnt.get(), st, rsl); if (rsl.sym) passes++; }
-            prims::exclusive_sum_u32(d_temp_, tile_cnt.get(), tile_off.get(), n_tiles, st);
-            const uint32_t nb1 = b1 < nv ? next_batch_end(b1, nv, nt, ntr) : b1;
-            real_range(b1, nb1, nr_lo, nr_hi, nrs);
-            const bool more = nt > 0 && !rsl.sym && !nrs.sym && !staged;      // (a batch of slices counts for itself)
-            gk::batch_fill(ctx, prefix_chars, r_lo, r_hi, tile_off.get(), X.key_a.get(), X.pos_a.get(), nr_lo, more ? nr_hi : nr_lo,
-                           more ? tile_cnt.get() : nullptr, st, rsl);
-            counted_lo = more ? b1 + 1 : 0; counted_hi = more ? nb1 + 1 : 0;
-            passes++;
-            if (vb[b0].slice) pass_end = b1;
-        }
+        feed.collect(b0, b1, X);
         RoundStats rs = sort_batch(X, B, ctx, d_temp_, S.err.get(), st, L.get(), &rmq);
         gk::batch_lcp(ctx, rmq, X.pos_b.get(), B, carry.get(), have_prev, L.get(), S.err.get(), st);
         MMT_HIP(hipMemcpyAsync(carry.get(), X.pos_b.get() + (B - 1), 8, hipMemcpyDeviceToDevice, st));
@@ -1294,13 +1254,7 @@ void Engine::guided_stream_expand(ScanState& SS, const mmt_params& p) {
             // window before ended in one of its slices)
             if (have_prev) ext = std::min<uint64_t>(std::min<uint64_t>(bins[vb[prev_last_bin].bin], prev_len), capped ? SS.ext0 : ~0ull);
             if (ext > head_room || ext > tail_len) throw std::runtime_error("guided sort: window head room too small");
-            if (ext) {
-                const uint64_t from = tail_len - ext;
-                MMT_HIP(hipMemcpyAsync(w_sa_[0].get(), t_sa.get() + from, ext * 4, hipMemcpyDeviceToDevice, st));
-                if (W) MMT_HIP(hipMemcpyAsync(w_hi_[0].get(), t_hi.get() + from, ext, hipMemcpyDeviceToDevice, st));
-                MMT_HIP(hipMemcpyAsync(w_bwt_[0].get(), t_bwt.get() + from, ext, hipMemcpyDeviceToDevice, st));
-                MMT_HIP(hipMemcpyAsync(w_lcp_[0].get(), t_lcp.get() + from, ext * 4, hipMemcpyDeviceToDevice, st));
-            }
+            if (ext) WinCols::copy(win, 0, tail, tail_len - ext, ext, st);
             S.first_tile.clear();
             // (stream entry base + 1 begins a bin or a slice, hence a group: its tile is where the window's groups begin; what the tile holds
             // of the window before is written once more, into the tail, with the same values)
@@ -1323,32 +1277,13 @@ void Engine::guided_stream_expand(ScanState& SS, const mmt_params& p) {
             uint64_t len = ext + wtotal;
             // what the next window may need of this one, before anything else touches the window
             tail_len = std::min<uint64_t>(len, head_room);
-            if (tail_len) {
-                const uint64_t from = len - tail_len;
-                MMT_HIP(hipMemcpyAsync(t_sa.get(), w_sa_[0].get() + from, tail_len * 4, hipMemcpyDeviceToDevice, st));
-                if (W) MMT_HIP(hipMemcpyAsync(t_hi.get(), w_hi_[0].get() + from, tail_len, hipMemcpyDeviceToDevice, st));
-                MMT_HIP(hipMemcpyAsync(t_bwt.get(), w_bwt_[0].get() + from, tail_len, hipMemcpyDeviceToDevice, st));
-                MMT_HIP(hipMemcpyAsync(t_lcp.get(), w_lcp_[0].get() + from, tail_len * 4, hipMemcpyDeviceToDevice, st));
-            }
+            if (tail_len) WinCols::copy(tail, 0, win, len - tail_len, tail_len, st);
             ColWindow w = window_view(0, base - ext, (uint32_t)len, (uint32_t)ext);
             // nothing an interval of this window could reach lies further left (bins) -- but for a window that continues a run bin:
             // there the cap of the mode bounds the reach (ext0), as between the windows of the parse proper
             w.more_left = vb[s0].slice && !vb[s0].first;
-            keep_window(w);
-            if (want_anchor_ranks_) {
-                SaCol piece = w.sa; piece.lo += ext; if (piece.hi) piece.hi += ext;
-                k::anchor_ranks(piece, base, wtotal, anchor, wide_ ? (void*)d_rank64_.get() : (void*)d_rank_.get(), st);
-            }
             const bool last_of_share = s1 == nv || base + wtotal == piece_end;
-            if (last_of_share && base + wtotal < n) {
-                MMT_HIP(hipMemsetAsync(w_lcp_[0].get() + len, 0, 4, st));
-                MMT_HIP(hipMemsetAsync(w_bwt_[0].get() + len, 0, 1, st));
-                MMT_HIP(hipMemsetAsync(w_sa_[0].get() + len, 0, 4, st));
-                if (W) MMT_HIP(hipMemsetAsync(w_hi_[0].get() + len, 0, 1, st));
-                w.len = (uint32_t)(len + 1);
-            }
-            if (!scan_window(SS, w, p)) throw std::runtime_error("guided sort: a walk left its bin");
-            sink_flush(SS);
+            if (!hand_off_window(SS, 0, w, p, last_of_share && base + wtotal < n)) throw std::runtime_error("guided sort: a walk left its bin");
             prev_len = len; have_prev = true;
             for (uint32_t b = s1; b-- > s0;) if (vb[b].count) { prev_last_bin = b; break; }
             base += wtotal; windows++;
@@ -1364,10 +1299,10 @@ void Engine::guided_stream_expand(ScanState& SS, const mmt_params& p) {
     guided_check_errors("text suffixes");
     if (base != piece_end) throw std::runtime_error("guided sort: the batches do not cover the text exactly once");
     S.rounds_dict = rounds_max; S.emit_launches = (uint32_t)windows;
-    text_passes_ = (uint32_t)passes; batches_ = (uint32_t)batches; staged_ = staged;
+    text_passes_ = (uint32_t)feed.passes(); batches_ = (uint32_t)batches; staged_ = staged;
     MMT_HIP(hipStreamSynchronize(st));
     const double ms = std::chrono::duration<double, std::milli>(now() - t0).count();
-    if (stats) std::fprintf(stderr, "[guided] expansion: %d passes over the text%s, %u slices of %u run bins\n", passes,
+    if (stats) std::fprintf(stderr, "[guided] expansion: %d passes over the text%s, %u slices of %u run bins\n", feed.passes(),
                             staged ? " (several batches per pass: staging list)" : "", run_slices_, sliced_bins);
     if (stats) std::fprintf(stderr, "[guided] expansion: %llu suffixes from %llu representatives (%llu in the whole text) in %d batches of at most %u "
                             "representatives, %d windows of at most %llu suffixes: %.1f ms (collect + sort + tables %.1f, emitter + scans %.1f); "

@@ -531,8 +531,8 @@ void Engine::pfp_emit_window(uint64_t b0, uint64_t c1, int set) {
     hipStream_t st = stream_;
     const uint64_t TILE = pk::emit_tile();
     pk::EmitArgs ea = S.ea;
-    ea.sa.lo = w_sa_[set].get(); ea.sa.hi = W ? w_hi_[set].get() : nullptr;
-    ea.bwt = w_bwt_[set].get(); ea.lcp = w_lcp_[set].get();
+    const WinCols cols = win_[set].cols(W);
+    ea.sa.lo = cols.sa; ea.sa.hi = cols.hi; ea.bwt = cols.bwt; ea.lcp = cols.lcp;
     ea.out_base = b0; ea.win_lo = b0; ea.win_hi = c1;
     // first tile: the one in which the group that covers stream entry b0 + 1 begins (looked up ahead of the windows
     // by pfp_stream: a read here waits behind the output piece of the window before, which is on its way to the host)
@@ -595,18 +595,13 @@ void Engine::pfp_stream(ScanState& SS, const mmt_params& p) {
     if (const char* c = std::getenv("MMT_SCAN_RANGE")) range = std::max<uint64_t>(1, std::strtoull(c, nullptr, 10));
     range = (std::max<uint64_t>(range, 1) + ALIGN_R - 1) / ALIGN_R * ALIGN_R;
     uint64_t lo = 0, hi = n;
-    shard_range(lo, hi);
+    shard_range(shard_index_, lo, hi);
     sort_pieces_.clear();
     for (uint32_t k = 0; k < shard_count_; k++) {
-        Engine* self = this;
-        const uint32_t keep = shard_index_;
-        self->shard_index_ = k;
         uint64_t a = 0, b = 0;
-        shard_range(a, b);
+        shard_range(k, a, b);
         sort_pieces_.emplace_back(a, b - a);
-        self->shard_index_ = keep;
     }
-    const uint64_t anchor = std::min<uint64_t>(doc_len_[0], n);
     // the first emitter tile of every window, while nothing else is queued (a window that has to be repeated with a longer
     // extension looks its tile up when it gets there)
     S.first_tile.clear();
@@ -628,15 +623,8 @@ void Engine::pfp_stream(ScanState& SS, const mmt_params& p) {
             ee.stop(st);
             stream_entries_ += len;
             if (std::getenv("MMT_EMIT_ABLATE")) break;       // timing of a crippled emitter (tests/micro/emit_ablate.sh): its windows are garbage
-            ColWindow w = window_view(0, b0, (uint32_t)len, (uint32_t)ext);
-            if (!scan_window(SS, w, p)) { ext = std::max<uint64_t>(ext * 4, SS.ext0); continue; }   // a walk ran off the extension
-            if (want_anchor_ranks_) {
-                SaCol piece = w.sa; piece.lo += ext; if (piece.hi) piece.hi += ext;
-                k::anchor_ranks(piece, c0, c1 - c0, anchor, wide_ ? (void*)d_rank64_.get() : (void*)d_rank_.get(), st);
-            }
-            keep_window(w);
-            sink_flush(SS);
-            break;
+            if (hand_off_window(SS, 0, window_view(0, b0, (uint32_t)len, (uint32_t)ext), p, false)) break;
+            ext = std::max<uint64_t>(ext * 4, SS.ext0);      // a walk ran off the extension
         }
     }
     if (read_u32(S.err.get(), st) && !std::getenv("MMT_EMIT_ABLATE")) {

@@ -40,7 +40,7 @@ static inline unsigned grid_for(uint64_t items, unsigned per_block) {
 // (newscan.hpp:266), which holds for every trigger with i >= w - 1.
 // Pass 1: one 16-bit mask per thread (16 consecutive positions) + the number of triggers per workgroup.
 // Pass 2 (after an exclusive scan of the workgroup counts): the trigger positions, ascending.
-constexpr uint32_t KR_PRIME = 1999999973u;             // newscan.hpp:86 (compile-time: reductions become multiplies)
+// (KR_PRIME: pfp_kernels.hpp)
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void k_trigger_masks(const TextRef T, uint64_t n, uint32_t w,
                                                          uint32_t p, uint32_t pot,

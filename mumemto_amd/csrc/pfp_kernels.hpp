@@ -14,6 +14,16 @@
 
 namespace mmt { namespace pk {
 
+// The Karp-Rabin fingerprint of the parse's trigger windows (newscan.hpp:84-114: this prime, base 256; compile-time: the
+// kernels' reductions become multiplies) and, on the host, its value for a window of w equal bytes c: a modulus that divides it
+// ends a phrase at EVERY position of a run of c (engine.cpp avoids such moduli, guided.cpp keeps such a run's bin whole).
+constexpr uint32_t KR_PRIME = 1999999973u;
+inline uint64_t kr_window_of_run(uint8_t c, uint32_t w) {
+    uint64_t h = 0;
+    for (uint32_t i = 0; i < w; i++) h = (h * 256 + c) % KR_PRIME;
+    return h;
+}
+
 // trigger positions in two passes: 16-bit masks (one per 16 text positions) + triggers per workgroup; then, given the
 // exclusive scan of those counts, the positions themselves (ascending)
 uint32_t trigger_blocks(uint64_t n);
