@@ -339,6 +339,27 @@ MMT_API int  mmt_comm_loopback(mmt_comm* c, uint64_t out[8]);
 /* One message of `elements` elements of `width` bytes (1, 4, 8) to this rank itself through ncclSend / ncclRecv in the pieces the
  * exchange cuts (MUMEMTO_RCCL_CHUNK): out = elements that arrived different, pieces, largest piece (bytes), microseconds.      */
 MMT_API int  mmt_comm_selftest(mmt_comm* c, uint64_t elements, uint32_t width, uint64_t out[4]);
+/* Every message of mmt_dist_merge / _merge_ranges / _gather_text is verified: the sender digests each piece of
+ * its send buffers and sends the digests behind the data in the same group (one ncclUint64 trailer per receiver), the receiver
+ * digests what arrived and compares on its GPU before anything reads the data.  A mismatch on ANY rank makes the call fail on
+ * EVERY rank (rc != 0; mmt_last_error names the detecting rank and, on that rank, peer, table, piece and bytes).
+ * MUMEMTO_EXCHANGE_VERIFY=0 switches it off; rank 0's value decides for all ranks.
+ * mmt_comm_verify_stats, counted since the communicator was created: out[0] messages digested (sent + received), [1] their
+ * pieces, [2] their bytes, [3] pieces that arrived different, [4] microseconds in the digest kernels (HIP events), [5] peer,
+ * [6] table (0 lengths, 1 offsets, 2 strands, 3 thresholds, 4 text, 5 digests = the trailer itself) and [7] piece of the first
+ * mismatch, all ones if there was none.                                                                                     */
+MMT_API int  mmt_comm_verify_stats(mmt_comm* c, uint64_t out[8]);
+/* The digest kernel by itself, for users with a transport of their own: `elements` elements of `width` bytes (1, 4, 8) at
+ * device_ptr (aligned to width, current device), cut into pieces of piece_elements; out_host gets two words per piece -- sum
+ * word, xor word -- for max(1, ceil(elements / piece_elements)) pieces.  For element i of a piece (0-based inside it) with
+ * value v zero-extended to 64 bits, mod 2^64:  x = v + (i + 1) * 0x9E3779B97F4A7C15;  x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;
+ * x ^= x >> 27;  x *= 0x94D049BB133111EB;  x ^= x >> 31;  sum += x;  xor ^= x.                                            */
+MMT_API int  mmt_exchange_digest(const void* device_ptr, uint64_t elements, uint32_t width, uint64_t piece_elements,
+                                 uint64_t* out_host);
+/* The same on a copy of a host array in a fresh device allocation, starting skip_elements into it (a base that is not
+ * 16-byte aligned); elements counts the whole array.                                                                        */
+MMT_API int  mmt_exchange_digest_host(const void* host_ptr, uint64_t elements, uint32_t width, uint64_t skip_elements,
+                                      uint64_t piece_elements, uint64_t* out_host);
 
 #ifdef __cplusplus
 }

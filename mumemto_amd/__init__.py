@@ -12,6 +12,7 @@ from .binding import (  # noqa: F401
     Engine,
     MumemtoError,
     Params,
+    exchange_digest,
     library_path,
     load_library,
     mumemto_mem,

@@ -80,7 +80,7 @@ GPU_ABI_SYMBOLS = [
     "mmt_device_memory", "mmt_engine_run_files", "mmt_anchor_merge_min_len", "mmt_pool_trim", "mmt_pool_set_reserve",
     "mmt_engine_set_scan_shard", "mmt_merged_from_rows", "mmt_anchor_merge_by_ranges", "mmt_dist_merge_ranges", "mmt_fold_slice_bounds", "mmt_comm_unique_id", "mmt_comm_create", "mmt_comm_destroy", "mmt_comm_loopback", "mmt_comm_selftest", "mmt_dist_merge",
     "mmt_dist_gather_text", "mmt_merged_write_text", "mmt_sort_pieces", "mmt_engine_keep_columns", "mmt_columns_kept",
-    "mmt_stream_stats", "mmt_engine_release_columns", "mmt_copy_thresh32", "mmt_thresh_device32", "mmt_engine_set_text_sink",
+    "mmt_comm_verify_stats", "mmt_exchange_digest", "mmt_exchange_digest_host", "mmt_stream_stats", "mmt_engine_release_columns", "mmt_copy_thresh32", "mmt_thresh_device32", "mmt_engine_set_text_sink",
     "mmt_engine_run_supplied",
 ]
 
@@ -187,6 +187,9 @@ def load_library():
     L.mmt_comm_destroy.argtypes = [C.c_void_p]
     L.mmt_comm_loopback.argtypes = [C.c_void_p, C.c_void_p]
     L.mmt_comm_selftest.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
+    L.mmt_comm_verify_stats.argtypes = [C.c_void_p, C.c_void_p]
+    L.mmt_exchange_digest.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p]
+    L.mmt_exchange_digest_host.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]
     L.mmt_dist_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
     L.mmt_dist_gather_text.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.mmt_partitions_used.restype = C.c_size_t
@@ -818,9 +821,39 @@ class Comm:
         _check(self.L.mmt_comm_selftest(self.h, int(elements), int(width), out))
         return {"different": int(out[0]), "pieces": int(out[1]), "largest_piece_bytes": int(out[2]), "seconds": int(out[3]) / 1e6}
 
+    TABLES = ("lengths", "offsets", "strands", "thresholds", "text", "digests")
+
+    def verify_stats(self):
+        """The verification of the exchange since this communicator was created (mmt_comm_verify_stats): messages, pieces and
+        bytes digested (sent + received), pieces that arrived different, seconds in the digest kernels, and the first mismatch
+        as {"peer", "table", "piece"} or None."""
+        out = (C.c_uint64 * 8)()
+        _check(self.L.mmt_comm_verify_stats(self.h, out))
+        none = int(out[5]) == 2 ** 64 - 1
+        first = None if none else {"peer": int(out[5]), "table": self.TABLES[int(out[6])], "piece": int(out[7])}
+        return {"messages": int(out[0]), "pieces": int(out[1]), "bytes": int(out[2]), "mismatches": int(out[3]),
+                "digest_seconds": int(out[4]) / 1e6, "first_mismatch": first}
+
     def gather_text(self):
         """Sharded modes (Engine.set_scan_shard): the whole output on rank 0, b"" elsewhere."""
         ptr, k = C.c_void_p(), C.c_size_t()
         _check(self.L.mmt_dist_gather_text(self.h, C.byref(ptr), C.byref(k)))
         return _bytes_at(ptr.value, k.value) if k.value else b""
 
+
+def exchange_digest(array, piece_elements, skip_elements=0):
+    """The exchange's digest kernel by itself (mmt_exchange_digest): the numpy array (uint8, uint32, int64 or uint64) is copied
+    into a fresh device allocation and digested from `skip_elements` elements into it, in pieces of `piece_elements`.
+    Returns uint64[pieces, 2]: the sum word and the xor word of every piece (an empty range is one piece of two zeros)."""
+    import numpy as np
+    L = load_library()
+    a = np.ascontiguousarray(array)
+    if a.ndim != 1 or a.dtype.itemsize not in (1, 4, 8) or a.dtype.kind not in "ui":
+        raise MumemtoError("exchange_digest: a one-dimensional integer array of 1, 4 or 8 bytes an element")
+    skip, piece = int(skip_elements), int(piece_elements)
+    if piece < 1 or not 0 <= skip <= a.size:
+        raise MumemtoError("exchange_digest: piece_elements >= 1 and 0 <= skip_elements <= len(array)")
+    n = a.size - skip
+    out = np.zeros((max(1, -(-n // piece)), 2), np.uint64)
+    _check(L.mmt_exchange_digest_host(a.ctypes.data, a.size, a.dtype.itemsize, skip, piece, out.ctypes.data))
+    return out

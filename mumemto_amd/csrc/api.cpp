@@ -9,12 +9,14 @@
 #include <cstring>
 #include <memory>
 #include <mutex>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "../../include/mumemto.h"
 #include "../../include/mumemto_gpu.h"
 #include "engine.hpp"
+#include "digest_kernels.hpp"
 #include "dist.hpp"
 #include "fasta.hpp"
 #include "merge.hpp"
@@ -544,7 +546,7 @@ int mmt_engine_set_producer(mmt_engine* e, int kind, uint32_t w, uint32_t p) {
     e->e->set_producer(kind, w, p);
     return 0;
 }
-int mmt_abi_version(void) { return 6; }
+int mmt_abi_version(void) { return 7; }
 int mmt_text_sink_digest(const mmt_engine* e, uint64_t out[2]) {
     if (!e || !out) return fail(1, "null");
     e->e->text_sink_digest(out);
@@ -777,6 +779,39 @@ int mmt_dist_gather_text(mmt_comm* c, const char** text, size_t* len) {
     MMT_TRY
     c->text = mmt::dist_gather_text(*c->c);
     *text = c->text.data(); *len = c->text.size();
+    MMT_CATCH
+}
+
+int mmt_comm_verify_stats(mmt_comm* c, uint64_t out[8]) {
+    if (!c || !out) return fail(1, "null");
+    MMT_TRY
+    mmt::comm_verify_stats(*c->c, out);
+    MMT_CATCH
+}
+
+// the digest kernel by itself: current device, default stream
+int mmt_exchange_digest(const void* device_ptr, uint64_t elements, uint32_t width, uint64_t piece_elements, uint64_t* out_host) {
+    if (!out_host || (!device_ptr && elements)) return fail(1, "null");
+    MMT_TRY
+    if (!piece_elements) throw std::runtime_error("mmt_exchange_digest: piece_elements must be positive");
+    const uint64_t pieces = mmt::dk::piece_count(elements, piece_elements);
+    mmt::DevBuf<uint64_t> d_out;
+    d_out.ensure(2 * pieces);
+    mmt::dk::digest_pieces(device_ptr, elements, width, piece_elements, d_out.get(), true, nullptr);
+    MMT_HIP(hipMemcpy(out_host, d_out.get(), 2 * pieces * 8, hipMemcpyDeviceToHost));
+    MMT_CATCH
+}
+// the same on a copy of a host array: the whole array goes into a fresh allocation, the digest starts skip_elements into it
+// (how a caller without device memory of its own -- the tests -- reaches a base that is not 16-byte aligned)
+int mmt_exchange_digest_host(const void* host_ptr, uint64_t elements, uint32_t width, uint64_t skip_elements, uint64_t piece_elements,
+                             uint64_t* out_host) {
+    if (!out_host || (!host_ptr && elements)) return fail(1, "null");
+    if (skip_elements > elements) return fail(1, "mmt_exchange_digest_host: skip_elements beyond the array");
+    MMT_TRY
+    mmt::DevBuf<uint8_t> d;
+    d.ensure(elements * width + 16);
+    if (elements) MMT_HIP(hipMemcpy(d.get(), host_ptr, elements * width, hipMemcpyHostToDevice));
+    if (mmt_exchange_digest(d.get() + skip_elements * width, elements - skip_elements, width, piece_elements, out_host)) return 3;
     MMT_CATCH
 }
 

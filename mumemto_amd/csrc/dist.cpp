@@ -25,6 +25,7 @@
 
 #include "engine.hpp"
 #include "merge.hpp"
+#include "digest_kernels.hpp"
 #include "dist.hpp"
 
 namespace mmt {
@@ -131,6 +132,10 @@ struct Comm {
     std::vector<std::unique_ptr<DevBuf<int64_t>>> off;
     std::vector<std::unique_ptr<DevBuf<uint8_t>>> st, text;
     std::vector<std::unique_ptr<DevBuf<uint32_t>>> th;      // thresholds travel at 32 bits
+    // verification of the exchange (run_step): digests of what this rank sends, the trailers it receives, digests of what arrived
+    DevBuf<uint64_t> d_sent, d_expected, d_got, d_verdict;
+    uint64_t stats[8] = {0, 0, 0, 0, 0, ~0ull, ~0ull, ~0ull};      // mmt_comm_verify_stats
+    std::string first_mismatch;                                  // this rank's first mismatch, in words
 };
 
 void comm_unique_id(uint8_t out[128]) {
@@ -179,14 +184,144 @@ static std::vector<uint64_t> exchange_meta(Comm& c, uint64_t w0, uint64_t w1, ui
 
 int comm_world(const Comm& c) { return c.world; }
 
-static MergedRows merge_on_rank0(Comm& c, uint32_t min_len, const std::vector<uint64_t>& meta);
-static MergedRows merge_by_ranges(Comm& c, uint32_t min_len, const std::vector<uint64_t>& meta);
+void comm_verify_stats(const Comm& c, uint64_t out[8]) { std::memcpy(out, c.stats, sizeof(c.stats)); }
+
+// ---- one exchange step, verified ----------------------------------------------------------------------------
+// Nothing below the exchange checks what arrives: round 6 measured a library that delivers a piece beyond 1 GiB with half its
+// elements changed and no error.  So every message travels with the digests of its pieces (digest_kernels.hpp): the sender
+// digests its send buffers on the engine's stream BEFORE the group and sends, per receiver, one trailer behind the data pieces
+// in the same group -- ncclUint64 (no other ncclSend / ncclRecv here has that type), two words per piece of every message to
+// that receiver in message order, then two words that are the digest of the trailer's own words before them (one piece): a
+// damaged trailer is told from damaged data.  After the group the receiver digests what arrived, compares ON THE DEVICE and
+// copies back a count and the first mismatch -- before anything consumes the data.  A step lists its messages in the order
+// they are posted (Step::send / recv), run_step does the rest.
+// MUMEMTO_EXCHANGE_VERIFY=0 switches all of it off (no digests, no trailers, no verdict); RANK 0's value decides for everybody
+// and travels in the first exchange_meta of a call (bit 1 of the fourth word), as the route does.
+enum Table { T_LENGTHS = 0, T_OFFSETS, T_STRANDS, T_THRESHOLDS, T_TEXT, T_DIGESTS };
+static const char* const kTableName[] = {"lengths", "offsets", "strands", "thresholds", "text", "digests"};
+
+static bool verify_wanted() {
+    const char* e = std::getenv("MUMEMTO_EXCHANGE_VERIFY");
+    return !(e && std::string(e) == "0");
+}
+
+struct Step {
+    struct Op { bool send; void* ptr; size_t count; ncclDataType_t type; uint32_t width; int peer; int table; size_t pair_at, pieces; };
+    std::vector<Op> ops;
+    template <typename T> void send(const T* buf, size_t count, ncclDataType_t t, int peer, int table) {
+        ops.push_back(Op{true, const_cast<T*>(buf), count, t, (uint32_t)sizeof(T), peer, table, 0, 0});
+    }
+    template <typename T> void recv(T* buf, size_t count, ncclDataType_t t, int peer, int table) {
+        ops.push_back(Op{false, buf, count, t, (uint32_t)sizeof(T), peer, table, 0, 0});
+    }
+};
+
+static void post(const Step::Op& o, Comm& c, hipStream_t st) {
+    if (o.width == 1) { if (o.send) send_pieces((const uint8_t*)o.ptr, o.count, o.type, o.peer, c.comm, st); else recv_pieces((uint8_t*)o.ptr, o.count, o.type, o.peer, c.comm, st); }
+    else if (o.width == 4) { if (o.send) send_pieces((const uint32_t*)o.ptr, o.count, o.type, o.peer, c.comm, st); else recv_pieces((uint32_t*)o.ptr, o.count, o.type, o.peer, c.comm, st); }
+    else { if (o.send) send_pieces((const uint64_t*)o.ptr, o.count, o.type, o.peer, c.comm, st); else recv_pieces((uint64_t*)o.ptr, o.count, o.type, o.peer, c.comm, st); }
+}
+
+// One group: the step's messages (+ trailers), stream synchronised behind it.  Returns the pieces that arrived different on
+// THIS rank (0 without verification); what the ranks do about it is a collective decision (check_verdict).
+static uint64_t run_step(Comm& c, Step& s, bool verify) {
+    hipStream_t st = c.engine->stream();
+    const size_t W = (size_t)c.world;
+    if (!verify) {
+        MMT_NCCL(rccl().GroupStart());
+        for (const Step::Op& o : s.ops) post(o, c, st);
+        MMT_NCCL(rccl().GroupEnd());
+        MMT_HIP(hipStreamSynchronize(st));
+        return 0;
+    }
+    // digest pairs per peer: those of its messages in message order, then the trailer's own
+    std::vector<size_t> s_pairs(W, 0), r_pairs(W, 0), s_at(W, 0), r_at(W, 0);
+    uint64_t bytes = 0, pieces = 0;
+    for (Step::Op& o : s.ops) {
+        o.pieces = (size_t)dk::piece_count(o.count, rccl_chunk_elements(o.width));
+        std::vector<size_t>& n = o.send ? s_pairs : r_pairs;
+        o.pair_at = n[(size_t)o.peer];                            // (relative to the peer's trailer until the bases are known)
+        n[(size_t)o.peer] += o.pieces;
+        bytes += o.count * o.width; pieces += o.pieces;
+    }
+    size_t s_total = 0, r_total = 0;
+    for (size_t p = 0; p < W; p++) {
+        if (s_pairs[p]) { s_at[p] = s_total; s_total += s_pairs[p] + 1; }
+        if (r_pairs[p]) { r_at[p] = r_total; r_total += r_pairs[p] + 1; }
+    }
+    for (Step::Op& o : s.ops) o.pair_at += (o.send ? s_at : r_at)[(size_t)o.peer];
+    c.d_sent.ensure(2 * s_total + 2); c.d_expected.ensure(2 * r_total + 2); c.d_got.ensure(2 * r_total + 2); c.d_verdict.ensure(3);
+    MMT_HIP(hipMemsetAsync(c.d_sent.get(), 0, (2 * s_total + 2) * 8, st));
+    MMT_HIP(hipMemsetAsync(c.d_got.get(), 0, (2 * r_total + 2) * 8, st));
+    uint64_t res[3] = {0, ~0ull, ~0ull};              // pairs that differ, the first data pair, the first trailer pair
+    MMT_HIP(hipMemcpyAsync(c.d_verdict.get(), res, sizeof(res), hipMemcpyHostToDevice, st));
+    EventPair t_send, t_recv;
+    t_send.start(st);
+    for (const Step::Op& o : s.ops)
+        if (o.send) dk::digest_pieces(o.ptr, o.count, o.width, rccl_chunk_elements(o.width), c.d_sent.get() + 2 * o.pair_at, false, st);
+    for (size_t p = 0; p < W; p++)
+        if (s_pairs[p]) dk::digest_pieces(c.d_sent.get() + 2 * s_at[p], 2 * s_pairs[p], 8, 2 * s_pairs[p], c.d_sent.get() + 2 * (s_at[p] + s_pairs[p]), false, st);
+    t_send.stop(st);
+    MMT_NCCL(rccl().GroupStart());
+    for (const Step::Op& o : s.ops) post(o, c, st);
+    for (size_t p = 0; p < W; p++) {
+        if (s_pairs[p]) send_pieces(c.d_sent.get() + 2 * s_at[p], 2 * (s_pairs[p] + 1), ncclUint64, (int)p, c.comm, st);
+        if (r_pairs[p]) recv_pieces(c.d_expected.get() + 2 * r_at[p], 2 * (r_pairs[p] + 1), ncclUint64, (int)p, c.comm, st);
+    }
+    MMT_NCCL(rccl().GroupEnd());
+    t_recv.start(st);
+    for (const Step::Op& o : s.ops)
+        if (!o.send) dk::digest_pieces(o.ptr, o.count, o.width, rccl_chunk_elements(o.width), c.d_got.get() + 2 * o.pair_at, false, st);
+    for (size_t p = 0; p < W; p++)
+        if (r_pairs[p]) dk::digest_pieces(c.d_expected.get() + 2 * r_at[p], 2 * r_pairs[p], 8, 2 * r_pairs[p], c.d_got.get() + 2 * (r_at[p] + r_pairs[p]), false, st);
+    t_recv.stop(st);
+    for (size_t p = 0; p < W; p++)
+        if (r_pairs[p]) dk::compare_digests(c.d_expected.get() + 2 * r_at[p], c.d_got.get() + 2 * r_at[p], r_pairs[p] + 1, r_at[p], c.d_verdict.get(), st);
+    MMT_HIP(hipMemcpyAsync(res, c.d_verdict.get(), sizeof(res), hipMemcpyDeviceToHost, st));
+    MMT_HIP(hipStreamSynchronize(st));
+    c.stats[0] += s.ops.size(); c.stats[1] += pieces; c.stats[2] += bytes; c.stats[3] += res[0];
+    c.stats[4] += (uint64_t)((t_send.ms() + t_recv.ms()) * 1000.0);
+    if (!res[0]) return 0;
+    // the first mismatch, by name: a trailer that does not match its own digest says nothing about the data of its peer
+    uint64_t peer = 0, table = T_DIGESTS, piece = 0, piece_bytes = 0;
+    if (res[2] != ~0ull) {
+        for (size_t p = 0; p < W; p++) if (r_pairs[p] && r_at[p] + r_pairs[p] == res[2]) { peer = p; piece_bytes = (r_pairs[p] + 1) * 16; }
+    } else {
+        for (const Step::Op& o : s.ops)
+            if (!o.send && res[1] >= o.pair_at && res[1] < o.pair_at + o.pieces) {
+                const size_t C = rccl_chunk_elements(o.width);
+                peer = (uint64_t)o.peer; table = (uint64_t)o.table; piece = res[1] - o.pair_at;
+                piece_bytes = std::min<uint64_t>(C, o.count - piece * C) * o.width;
+            }
+    }
+    if (c.stats[5] == ~0ull) { c.stats[5] = peer; c.stats[6] = table; c.stats[7] = piece; }
+    c.first_mismatch = "from peer " + std::to_string(peer) + ", table " + kTableName[table] + ", piece " + std::to_string(piece) + ", " +
+                       std::to_string(piece_bytes) + " bytes";
+    return res[0];
+}
+
+// The verdict is collective: a rank that threw alone would leave its peers waiting in the next collective.  `all` holds every
+// rank's four words of an exchange_meta whose fourth word is that rank's run_step result; if any is set, EVERY rank throws.
+static void check_verdict(const Comm& c, const std::vector<uint64_t>& all) {
+    std::string who;
+    for (int r = 0; r < c.world; r++)
+        if (all[(size_t)r * 4 + 3])
+            who += (who.empty() ? "rank " : ", rank ") + std::to_string(r) + " detected " + std::to_string(all[(size_t)r * 4 + 3]) + " mismatching piece(s)";
+    if (who.empty()) return;
+    std::string msg = "exchange verification failed: " + who;
+    if (all[(size_t)c.rank * 4 + 3]) msg += "; the first on rank " + std::to_string(c.rank) + " arrived " + c.first_mismatch;
+    throw std::runtime_error(msg + " (the digests of a message's pieces did not match what arrived: DESIGN.md 8a)");
+}
+
+static MergedRows merge_on_rank0(Comm& c, uint32_t min_len, const std::vector<uint64_t>& meta, bool verify);
+static MergedRows merge_by_ranges(Comm& c, uint32_t min_len, const std::vector<uint64_t>& meta, bool verify);
 
 // Strict multi-MUMs.  The engine's last run must have been this rank's partition with merge metadata on.
 // Returns the merged rows on rank 0 (already in direct-run order), an empty MergedRows elsewhere.
 // route: 0 = rank 0 folds everything, 1 = every rank folds its slice of the anchor, -1 = automatic (slices from four ranks
 // on; MUMEMTO_RANGE_FOLD=0/1 overrides).  The route is a collective decision: every rank sends its wish with the table
 // sizes and all of them follow RANK 0's -- ranks whose environments differ must not end up in different collectives.
+// The same holds for MUMEMTO_EXCHANGE_VERIFY (bit 1 of the same word): it decides how many messages a group holds.
 static MergedRows merge_routed(Comm& c, uint32_t min_len, bool* is_root, int route) {
     Engine& e = *c.engine;
     MMT_HIP(hipSetDevice(e.device()));
@@ -200,16 +335,17 @@ static MergedRows merge_routed(Comm& c, uint32_t min_len, bool* is_root, int rou
     const uint32_t* my_len; const int64_t* my_off; const uint8_t* my_st;
     e.rows_mum_device(&my_len, &my_off, &my_st);
     const uint32_t my_longest = longest_row(e, my_len, R.n_rows, true);
-    const std::vector<uint64_t> meta = exchange_meta(c, R.n_rows, R.n_docs, my_longest, (uint64_t)route);
+    const std::vector<uint64_t> meta = exchange_meta(c, R.n_rows, R.n_docs, my_longest, (uint64_t)route | (verify_wanted() ? 2 : 0));
     for (int r = 1; r < c.world; r++)
         if (meta[(size_t)r * 4 + 1] == 0) throw std::runtime_error("a rank without documents in the exchange");
-    return meta[3] ? merge_by_ranges(c, min_len, meta) : merge_on_rank0(c, min_len, meta);
+    const bool verify = (meta[3] & 2) && c.world > 1;               // (a world of one exchanges nothing)
+    return (meta[3] & 1) ? merge_by_ranges(c, min_len, meta, verify) : merge_on_rank0(c, min_len, meta, verify);
 }
 
 MergedRows dist_merge(Comm& c, uint32_t min_len, bool* is_root) { return merge_routed(c, min_len, is_root, -1); }
 MergedRows dist_merge_ranges(Comm& c, uint32_t min_len, bool* is_root) { return merge_routed(c, min_len, is_root, 1); }
 
-static MergedRows merge_on_rank0(Comm& c, uint32_t min_len, const std::vector<uint64_t>& meta) {
+static MergedRows merge_on_rank0(Comm& c, uint32_t min_len, const std::vector<uint64_t>& meta, bool verify) {
     Engine& e = *c.engine;
     hipStream_t st = e.stream();
     const HostRows& R = e.rows_meta();
@@ -220,29 +356,29 @@ static MergedRows merge_on_rank0(Comm& c, uint32_t min_len, const std::vector<ui
     // nothing of the others -- with a whole genome as the anchor a threshold column is 6 GB, and broadcasting every
     // rank's to every rank (round 2) put 8 x 6 GB into each rank's HBM for nothing.  Rank 0's own tables stay where the
     // engine has them.
-    MMT_NCCL(rccl().GroupStart());
+    Step step;
     if (c.rank != 0) {
         const size_t rows = R.n_rows, cells = rows * R.n_docs;
         if (rows) {
-            send_pieces(my_len, rows, ncclUint32, 0, c.comm, st);
-            send_pieces(my_off, cells, ncclInt64, 0, c.comm, st);
-            send_pieces(my_st, cells, ncclUint8, 0, c.comm, st);
+            step.send(my_len, rows, ncclUint32, 0, T_LENGTHS);
+            step.send(my_off, cells, ncclInt64, 0, T_OFFSETS);
+            step.send(my_st, cells, ncclUint8, 0, T_STRANDS);
         }
-        send_pieces(e.thresh_device32(), L, ncclUint32, 0, c.comm, st);
+        step.send(e.thresh_device32(), L, ncclUint32, 0, T_THRESHOLDS);
     } else {
         for (int r = 1; r < c.world; r++) {
             const size_t rows = meta[(size_t)r * 4], docs = meta[(size_t)r * 4 + 1], cells = rows * docs;
             c.len[r]->ensure(rows + 1); c.off[r]->ensure(cells + 1); c.st[r]->ensure(cells + 1); c.th[r]->ensure(L);
             if (rows) {
-                recv_pieces(c.len[r]->get(), rows, ncclUint32, r, c.comm, st);
-                recv_pieces(c.off[r]->get(), cells, ncclInt64, r, c.comm, st);
-                recv_pieces(c.st[r]->get(), cells, ncclUint8, r, c.comm, st);
+                step.recv(c.len[r]->get(), rows, ncclUint32, r, T_LENGTHS);
+                step.recv(c.off[r]->get(), cells, ncclInt64, r, T_OFFSETS);
+                step.recv(c.st[r]->get(), cells, ncclUint8, r, T_STRANDS);
             }
-            recv_pieces(c.th[r]->get(), L, ncclUint32, r, c.comm, st);
+            step.recv(c.th[r]->get(), L, ncclUint32, r, T_THRESHOLDS);
         }
     }
-    MMT_NCCL(rccl().GroupEnd());
-    MMT_HIP(hipStreamSynchronize(st));
+    const uint64_t bad = run_step(c, step, verify);
+    if (verify) check_verdict(c, exchange_meta(c, 0, 0, 0, bad));          // before the fold reads a byte of what arrived
     if (c.rank != 0) return MergedRows();
     std::vector<mmt_partition> parts((size_t)c.world);
     for (int r = 0; r < c.world; r++) {
@@ -280,7 +416,7 @@ static MergedRows merge_on_rank0(Comm& c, uint32_t min_len, const std::vector<ui
 // genomes a rank's table is 30 million rows x 13 columns = 3.5 GB, and seven of them arrived on every rank to be filtered
 // down to an eighth.)  The pieces go to rank 0 in rank order = anchor order.  Rank 0's work drops from world - 1 fold steps
 // over the whole anchor to world - 1 steps over 1 / world of it.
-static MergedRows merge_by_ranges(Comm& c, uint32_t min_len, const std::vector<uint64_t>& meta) {
+static MergedRows merge_by_ranges(Comm& c, uint32_t min_len, const std::vector<uint64_t>& meta, bool verify) {
     Engine& e = *c.engine;
     hipStream_t st = e.stream();
     const HostRows& R = e.rows_meta();
@@ -323,29 +459,28 @@ static MergedRows merge_by_ranges(Comm& c, uint32_t min_len, const std::vector<u
         MMT_HIP(hipMemcpyAsync(counts.data(), d_all.get(), counts.size() * 8, hipMemcpyDeviceToHost, st));
         MMT_HIP(hipStreamSynchronize(st));
     }
-    MMT_NCCL(rccl().GroupStart());
+    Step slices;
     for (int r = 0; r < W; r++) {
         if (r == c.rank) continue;
         // to rank r: my rows of its range, my thresholds of its range
         const size_t s_rows = out[r]->n, s_cells = s_rows * R.n_docs;
         if (s_rows) {
-            send_pieces(out[r]->len.get(), s_rows, ncclUint32, r, c.comm, st);
-            send_pieces(out[r]->off.get(), s_cells, ncclInt64, r, c.comm, st);
-            send_pieces(out[r]->str.get(), s_cells, ncclUint8, r, c.comm, st);
+            slices.send(out[r]->len.get(), s_rows, ncclUint32, r, T_LENGTHS);
+            slices.send(out[r]->off.get(), s_cells, ncclInt64, r, T_OFFSETS);
+            slices.send(out[r]->str.get(), s_cells, ncclUint8, r, T_STRANDS);
         }
-        send_pieces(e.thresh_device32() + base[r], hi[r] - base[r], ncclUint32, r, c.comm, st);
+        slices.send(e.thresh_device32() + base[r], hi[r] - base[r], ncclUint32, r, T_THRESHOLDS);
         // from rank r: its rows of my range, its thresholds of my range
         const size_t rows = counts[(size_t)r * W + c.rank], docs = meta[(size_t)r * 4 + 1], cells = rows * docs;
         c.len[r]->ensure(rows + 1); c.off[r]->ensure(cells + 1); c.st[r]->ensure(cells + 1); c.th[r]->ensure(my_span + 1);
         if (rows) {
-            recv_pieces(c.len[r]->get(), rows, ncclUint32, r, c.comm, st);
-            recv_pieces(c.off[r]->get(), cells, ncclInt64, r, c.comm, st);
-            recv_pieces(c.st[r]->get(), cells, ncclUint8, r, c.comm, st);
+            slices.recv(c.len[r]->get(), rows, ncclUint32, r, T_LENGTHS);
+            slices.recv(c.off[r]->get(), cells, ncclInt64, r, T_OFFSETS);
+            slices.recv(c.st[r]->get(), cells, ncclUint8, r, T_STRANDS);
         }
-        recv_pieces(c.th[r]->get(), my_span, ncclUint32, r, c.comm, st);
+        slices.recv(c.th[r]->get(), my_span, ncclUint32, r, T_THRESHOLDS);
     }
-    MMT_NCCL(rccl().GroupEnd());
-    MMT_HIP(hipStreamSynchronize(st));
+    const uint64_t bad_slices = run_step(c, slices, verify);
     // this rank's slice
     std::vector<mmt_partition> parts((size_t)W);
     for (int r = 0; r < W; r++) {
@@ -362,20 +497,24 @@ static MergedRows merge_by_ranges(Comm& c, uint32_t min_len, const std::vector<u
         }
         p.thresh_len = L; p.thresh_on_device = 1; p.rows_on_device = 1; p.thresh_bits = 32;
     }
-    MergedRows piece = anchor_merge_slice(e, parts.data(), parts.size(), min_len, lo[c.rank], hi[c.rank], base[c.rank], true);
+    // (a rank whose slices arrived damaged folds nothing -- nothing consumes what did not verify -- and says so in the spare
+    // word of the meta exchange every rank is on its way to: all of them fail there together)
+    MergedRows piece;
+    if (!bad_slices) piece = anchor_merge_slice(e, parts.data(), parts.size(), min_len, lo[c.rank], hi[c.rank], base[c.rank], true);
     out.clear();
     // the pieces to rank 0, in rank order
-    const std::vector<uint64_t> pm = exchange_meta(c, piece.n_rows, piece.n_docs, 0);
+    const std::vector<uint64_t> pm = exchange_meta(c, piece.n_rows, piece.n_docs, 0, bad_slices);
+    check_verdict(c, pm);
     std::vector<MergedRows> pieces;
-    MMT_NCCL(rccl().GroupStart());
+    Step gather;
     if (c.rank != 0) {
         const size_t rows = piece.n_rows, cells = rows * piece.n_docs;
         if (rows) {
-            send_pieces(piece.d_length.get(), rows, ncclUint32, 0, c.comm, st);
-            send_pieces(piece.d_offsets.get(), cells, ncclInt64, 0, c.comm, st);
-            send_pieces(piece.d_strands.get(), cells, ncclUint8, 0, c.comm, st);
+            gather.send(piece.d_length.get(), rows, ncclUint32, 0, T_LENGTHS);
+            gather.send(piece.d_offsets.get(), cells, ncclInt64, 0, T_OFFSETS);
+            gather.send(piece.d_strands.get(), cells, ncclUint8, 0, T_STRANDS);
         }
-        send_pieces(piece.d_thresh.get(), piece.thresh_len, ncclUint32, 0, c.comm, st);
+        gather.send(piece.d_thresh.get(), piece.thresh_len, ncclUint32, 0, T_THRESHOLDS);
     } else {
         pieces.resize((size_t)W);
         pieces[0] = std::move(piece);
@@ -385,15 +524,15 @@ static MergedRows merge_by_ranges(Comm& c, uint32_t min_len, const std::vector<u
             const size_t cells = p.n_rows * p.n_docs;
             p.d_length.ensure(p.n_rows + 1); p.d_offsets.ensure(cells + 1); p.d_strands.ensure(cells + 1); p.d_thresh.ensure(p.thresh_len + 1);
             if (p.n_rows) {
-                recv_pieces(p.d_length.get(), p.n_rows, ncclUint32, r, c.comm, st);
-                recv_pieces(p.d_offsets.get(), cells, ncclInt64, r, c.comm, st);
-                recv_pieces(p.d_strands.get(), cells, ncclUint8, r, c.comm, st);
+                gather.recv(p.d_length.get(), p.n_rows, ncclUint32, r, T_LENGTHS);
+                gather.recv(p.d_offsets.get(), cells, ncclInt64, r, T_OFFSETS);
+                gather.recv(p.d_strands.get(), cells, ncclUint8, r, T_STRANDS);
             }
-            recv_pieces(p.d_thresh.get(), p.thresh_len, ncclUint32, r, c.comm, st);
+            gather.recv(p.d_thresh.get(), p.thresh_len, ncclUint32, r, T_THRESHOLDS);
         }
     }
-    MMT_NCCL(rccl().GroupEnd());
-    MMT_HIP(hipStreamSynchronize(st));
+    const uint64_t bad_pieces = run_step(c, gather, verify);
+    if (verify) check_verdict(c, exchange_meta(c, 0, 0, 0, bad_pieces));
     if (c.rank != 0) return MergedRows();
     MergedRows m = concat_pieces(e, pieces);
     sort_like_direct(e, m);
@@ -521,24 +660,25 @@ std::string dist_gather_text(Comm& c) {
     MMT_HIP(hipSetDevice(e.device()));
     hipStream_t st = e.stream();
     const HostRows& R = e.rows(Engine::ROWS_TEXT);
-    const std::vector<uint64_t> meta = exchange_meta(c, R.n_rows, R.n_docs, R.text_len);
+    const std::vector<uint64_t> meta = exchange_meta(c, R.n_rows, R.n_docs, R.text_len, verify_wanted() ? 2 : 0);
+    const bool verify = (meta[3] & 2) && c.world > 1;               // rank 0's word, as in merge_routed
     DevBuf<uint8_t> mine;
     if (c.rank != 0) {
         mine.ensure(R.text_len + 1);
         if (R.text_len) MMT_HIP(hipMemcpyAsync(mine.get(), R.text, R.text_len, hipMemcpyHostToDevice, st));
     }
-    MMT_NCCL(rccl().GroupStart());
+    Step step;
     if (c.rank != 0) {
-        if (R.text_len) send_pieces(mine.get(), R.text_len, ncclUint8, 0, c.comm, st);
+        if (R.text_len) step.send(mine.get(), R.text_len, ncclUint8, 0, T_TEXT);
     } else {
         for (int r = 1; r < c.world; r++) {
             const size_t bytes = meta[(size_t)r * 4 + 2];
             c.text[r]->ensure(bytes + 1);
-            if (bytes) recv_pieces(c.text[r]->get(), bytes, ncclUint8, r, c.comm, st);
+            if (bytes) step.recv(c.text[r]->get(), bytes, ncclUint8, r, T_TEXT);
         }
     }
-    MMT_NCCL(rccl().GroupEnd());
-    MMT_HIP(hipStreamSynchronize(st));
+    const uint64_t bad = run_step(c, step, verify);
+    if (verify) check_verdict(c, exchange_meta(c, 0, 0, 0, bad));          // before the bytes go to the host
     if (c.rank != 0) return std::string();
     size_t total = 0;
     for (int r = 0; r < c.world; r++) total += meta[(size_t)r * 4 + 2];

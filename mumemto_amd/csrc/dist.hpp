@@ -15,6 +15,8 @@ void comm_destroy(Comm* c);
 MergedRows dist_merge(Comm& c, uint32_t min_len, bool* is_root);                  // collective; rows on rank 0
 MergedRows dist_merge_ranges(Comm& c, uint32_t min_len, bool* is_root);           // the same, every rank folds its slice of the anchor
 int comm_world(const Comm& c);
+// the verification of the exchange since the communicator was created (mmt_comm_verify_stats in mumemto_gpu.h)
+void comm_verify_stats(const Comm& c, uint64_t out[8]);
 std::string dist_gather_text(Comm& c);                                            // collective; bytes on rank 0
 void dist_loopback(Comm& c, uint64_t out[8]);
 void dist_selftest(Comm& c, uint64_t elements, uint32_t width, uint64_t out[4]);     // one message of that size to this rank itself, in pieces                                     // the exchange's messages with this rank as its own peer
