@@ -299,6 +299,33 @@ MMT_API int mmt_merged_device(const mmt_merged* m, const uint32_t** length, cons
 MMT_API int mmt_merged_from_rows(mmt_engine* e, const uint32_t* length, const int64_t* offsets, const uint8_t* strands,
                                  size_t n_rows, size_t n_docs, const uint16_t* thresh, size_t thresh_len,
                                  mmt_merged** out);
+/* The device twin: row tables that already sit in the HBM of e's GPU (mmt_rows_mum_device of a direct run) become a merged
+ * result without a round trip through the host; the tables are copied, so the result outlives the engine's next run.
+ * It carries no thresholds.                                                                                            */
+MMT_API int mmt_merged_from_rows_device(mmt_engine* e, const uint32_t* length, const int64_t* offsets,
+                                        const uint8_t* strands, size_t n_rows, size_t n_docs, mmt_merged** out);
+/* ---- collinear blocks (`mumemto collinear`: mumemto/collinear_block.py on mumemto/utils.py find_coll_blocks) ----------
+ * Callers detect these entry points by their symbols; mmt_abi_version() did not change for them.
+ * mmt_merged_collinear does on the device what the reference does between reading a .mums file and writing the sorted one:
+ * rows with an absent document (-1) are dropped, the rest is put into ascending order of column 0 (stable), and every
+ * maximal run of consecutive rows that are consecutive, in the direction of their strand, in EVERY column is a block
+ * (first row, last row), first < last.  max_break > 0 also cuts a run between two rows whose gap in some column exceeds it
+ * (0: no limit; the tool's default is 1000); min_singleton_length >= 0 makes every row outside all runs whose length is at
+ * least that a block of its own (negative: none).  Blocks are numbered by their first row.  Equal starts within one column
+ * are ordered by row, where the reference leaves the order to an unstable sort.  Fewer than 2^32 rows.
+ * The blocks are attached to m and m's table becomes the filtered, sorted one: from here on mmt_merged_rows / _get / _device
+ * / _text / _write_text answer for that table, and the text carries a fourth field, the block number or `-`.  Calling it
+ * again recomputes the blocks; mmt_merged_sort_like_direct drops them.                                                   */
+MMT_API int mmt_merged_collinear(mmt_engine* e, mmt_merged* m, uint32_t max_break, int64_t min_singleton_length,
+                                 uint64_t* n_blocks);
+/* lr receives 2 x n_blocks host entries: first row, last row of every block                                            */
+MMT_API int mmt_merged_blocks(const mmt_merged* m, uint32_t* lr);
+/* the same list in HBM, and the block of every row (0xFFFFFFFF: none); owned by m                                      */
+MMT_API int mmt_merged_blocks_device(const mmt_merged* m, const uint32_t** lr, const uint32_t** row_block);
+/* Of the last mmt_merged_collinear on m: out[0..4] HIP-event milliseconds of filter + sort of the table, column extraction,
+ * column sorts, adjacency passes, blocks; [5] rows before, [6] rows kept, [7] columns that needed a sort, [8] columns found
+ * ascending, [9] column batches, [10] 1 when the table itself was re-ordered, [11] blocks.                               */
+MMT_API int mmt_merged_collinear_stats(const mmt_merged* m, double out[12]);
 /* Re-order merged rows into the order of a direct run (lexicographic by match
  * string) using the anchor suffix ranks of the engine's last run, whose
  * document 0 must be the anchor.                              */

@@ -10,7 +10,9 @@ from .binding import (  # noqa: F401
     Comm,
     DevicePartition,
     Engine,
+    Merged,
     MumemtoError,
+    collinear_blocks,
     Params,
     exchange_digest,
     library_path,

@@ -81,7 +81,8 @@ GPU_ABI_SYMBOLS = [
     "mmt_engine_set_scan_shard", "mmt_merged_from_rows", "mmt_anchor_merge_by_ranges", "mmt_dist_merge_ranges", "mmt_fold_slice_bounds", "mmt_comm_unique_id", "mmt_comm_create", "mmt_comm_destroy", "mmt_comm_loopback", "mmt_comm_selftest", "mmt_dist_merge",
     "mmt_dist_gather_text", "mmt_merged_write_text", "mmt_sort_pieces", "mmt_engine_keep_columns", "mmt_columns_kept",
     "mmt_comm_verify_stats", "mmt_exchange_digest", "mmt_exchange_digest_host", "mmt_stream_stats", "mmt_engine_release_columns", "mmt_copy_thresh32", "mmt_thresh_device32", "mmt_engine_set_text_sink",
-    "mmt_engine_run_supplied",
+    "mmt_engine_run_supplied", "mmt_merged_from_rows_device", "mmt_merged_collinear", "mmt_merged_blocks",
+    "mmt_merged_blocks_device", "mmt_merged_collinear_stats",
 ]
 
 
@@ -182,6 +183,12 @@ def load_library():
                                        C.c_uint64, C.POINTER(C.c_double)]
     L.mmt_merged_from_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p,
                                        C.c_size_t, C.POINTER(C.c_void_p)]
+    L.mmt_merged_from_rows_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                              C.POINTER(C.c_void_p)]
+    L.mmt_merged_collinear.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int64, C.POINTER(C.c_uint64)]
+    L.mmt_merged_blocks.argtypes = [C.c_void_p, C.c_void_p]
+    L.mmt_merged_blocks_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.mmt_merged_collinear_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.mmt_comm_unique_id.argtypes = [C.c_void_p]
     L.mmt_comm_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
     L.mmt_comm_destroy.argtypes = [C.c_void_p]
@@ -759,6 +766,145 @@ def _engine_rows_in_direct_order(self, length, offsets, strands, thresh=None):
 
 
 Engine.rows_in_direct_order = _engine_rows_in_direct_order
+
+
+class Merged:
+    """A row table in the HBM of an engine's GPU (mmt_merged of mumemto_gpu.h): the result of a fold, or rows handed over
+    with Merged.from_rows / Merged.from_device.  collinear() computes the collinear blocks of its rows on the device."""
+
+    def __init__(self, engine, handle):
+        self.engine, self.L, self.h = engine, engine.L, handle
+
+    @classmethod
+    def from_rows(cls, engine, lengths, starts, strands):
+        """host arrays: lengths u32 [n], starts i64 [n, N] (-1 = absent), strands bool / u8 [n, N] (1 = '+')"""
+        lengths = np.ascontiguousarray(lengths, np.uint32)
+        starts = np.ascontiguousarray(starts, np.int64)
+        if starts.ndim != 2:
+            starts = starts.reshape(len(lengths), -1)
+        strands = np.ascontiguousarray(np.asarray(strands).astype(np.uint8)).reshape(starts.shape)
+        m = C.c_void_p()
+        _check(engine.L.mmt_merged_from_rows(engine.h, _p(lengths), _p(starts), _p(strands), len(lengths), starts.shape[1],
+                                             None, 0, C.byref(m)))
+        return cls(engine, m)
+
+    @classmethod
+    def from_device(cls, engine, n_rows, n_docs, length_ptr, offsets_ptr, strands_ptr):
+        """tables already in the engine's HBM, e.g. Merged.from_device(eng, *eng.rows_mum_device()); they are copied"""
+        m = C.c_void_p()
+        _check(engine.L.mmt_merged_from_rows_device(engine.h, C.c_void_p(length_ptr), C.c_void_p(offsets_ptr),
+                                                    C.c_void_p(strands_ptr), int(n_rows), int(n_docs), C.byref(m)))
+        return cls(engine, m)
+
+    @classmethod
+    def from_partitions(cls, engine, parts, min_len=20):
+        """the anchor fold of partitions, kept as a handle (Engine.anchor_merge copies the result out and frees it): parts are
+        DevicePartition objects or (length u32 [n], offsets i64 [n, nd], strands u8 [n, nd], thresh u16 / u32) host tuples"""
+        arr = (Partition * len(parts))()
+        keep = []
+        for i, part in enumerate(parts):
+            if isinstance(part, DevicePartition):
+                arr[i] = Partition(part.n_rows, part.n_docs, part.length_ptr, part.offsets_ptr, part.strands_ptr,
+                                   part.thresh_ptr, part.thresh_len, 1, 1, part.thresh_bits)
+                continue
+            length = np.ascontiguousarray(part[0], np.uint32)
+            off = np.ascontiguousarray(part[1], np.int64).reshape(len(length), -1)
+            st = np.ascontiguousarray(part[2], np.uint8).reshape(off.shape)
+            bits = 32 if part[3].dtype == np.uint32 else 16
+            th = np.ascontiguousarray(part[3], np.uint32 if bits == 32 else np.uint16)
+            keep += [length, off, st, th]
+            arr[i] = Partition(len(length), off.shape[1], _p(length).value, _p(off).value, _p(st).value, _p(th).value,
+                               len(th), 0, 0, bits)
+        m = C.c_void_p()
+        _check(engine.L.mmt_anchor_merge_min_len(engine.h, arr, len(parts), C.c_uint32(min_len), C.byref(m)))
+        return cls(engine, m)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.mmt_merged_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def n_rows(self):
+        return int(self.L.mmt_merged_rows(self.h))
+
+    @property
+    def n_docs(self):
+        return int(self.L.mmt_merged_docs(self.h))
+
+    def rows(self):
+        """(lengths u32 [n], starts i64 [n, N], strands u8 [n, N]) copied to the host"""
+        n, nd = self.n_rows, self.n_docs
+        length = np.zeros(max(n, 1), np.uint32)
+        off = np.zeros((max(n, 1), nd), np.int64)
+        st = np.zeros((max(n, 1), nd), np.uint8)
+        _check(self.L.mmt_merged_get(self.h, _p(length), _p(off), _p(st), None))
+        return length[:n], off[:n], st[:n]
+
+    def collinear(self, max_break=1000, min_singleton_length=None):
+        """Collinear blocks as the reference's `mumemto collinear` finds them: (n_blocks, 2) uint32, first and last row of
+        every block.  The table becomes the filtered (no partial rows), sorted (by column 0) one the rows refer to, and
+        text() / write_text() carry the block of every row as a fourth field from here on."""
+        k = C.c_uint64()
+        single = -1 if min_singleton_length is None else int(min_singleton_length)
+        _check(self.L.mmt_merged_collinear(self.engine.h, self.h, C.c_uint32(int(max_break)), C.c_int64(single), C.byref(k)))
+        return self.blocks()
+
+    def blocks(self):
+        st = (C.c_double * 12)()
+        _check(self.L.mmt_merged_collinear_stats(self.h, st))
+        lr = np.zeros((int(st[11]), 2), np.uint32)
+        _check(self.L.mmt_merged_blocks(self.h, _p(lr) if len(lr) else None))
+        return lr
+
+    def blocks_device(self):
+        """(address of the u32 [n_blocks, 2] block list, address of the u32 [n_rows] block of every row) in HBM"""
+        a, b = C.c_void_p(), C.c_void_p()
+        _check(self.L.mmt_merged_blocks_device(self.h, C.byref(a), C.byref(b)))
+        return a.value or 0, b.value or 0
+
+    def collinear_stats(self):
+        st = (C.c_double * 12)()
+        _check(self.L.mmt_merged_collinear_stats(self.h, st))
+        names = ["filter_sort_ms", "extract_ms", "sort_ms", "adjacency_ms", "blocks_ms"]
+        d = {k: float(st[i]) for i, k in enumerate(names)}
+        d.update(rows_in=int(st[5]), rows_kept=int(st[6]), cols_sorted=int(st[7]), cols_ascending=int(st[8]),
+                 batches=int(st[9]), table_sorted=bool(st[10]), n_blocks=int(st[11]))
+        return d
+
+    def text(self):
+        k = C.c_size_t()
+        ptr = self.L.mmt_merged_text(self.h, C.byref(k))
+        if not ptr and self.n_rows:
+            raise MumemtoError(self.L.mmt_last_error().decode())
+        return _bytes_at(ptr, k.value)
+
+    def write_text(self, path):
+        _check(self.L.mmt_merged_write_text(self.h, os.fsencode(path)))
+
+
+def collinear_blocks(lengths, starts, strands, max_break=1000, min_singleton_length=None, device=0):
+    """Rows on the host -> ((lengths, starts, strands) of the filtered, sorted table, blocks u32 [n_blocks, 2])."""
+    eng = Engine(device)
+    try:
+        with Merged.from_rows(eng, lengths, starts, strands) as m:
+            blocks = m.collinear(max_break, min_singleton_length)
+            length, off, st = m.rows()
+            return (length, off, st.astype(bool)), blocks
+    finally:
+        eng.close()
 
 
 class Comm:

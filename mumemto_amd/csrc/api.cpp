@@ -20,6 +20,7 @@
 #include "dist.hpp"
 #include "fasta.hpp"
 #include "merge.hpp"
+#include "collinear.hpp"
 
 namespace {
 
@@ -101,6 +102,7 @@ struct mmt_merged {
     std::string text;
     mmt::Engine* engine = nullptr;     // the engine whose device and stream the rows live on
     bool text_valid = false;
+    mmt::CollinearStats coll;          // of the last mmt_merged_collinear
 };
 
 extern "C" {
@@ -720,6 +722,68 @@ int mmt_merged_from_rows(mmt_engine* e, const uint32_t* length, const int64_t* o
     m->engine = e->e.get();
     *out = m.release();
     MMT_CATCH
+}
+// the device twin: the tables are copied HBM -> HBM (the rows of mmt_rows_mum_device live until the engine's next run)
+int mmt_merged_from_rows_device(mmt_engine* e, const uint32_t* length, const int64_t* offsets, const uint8_t* strands,
+                                size_t n_rows, size_t n_docs, mmt_merged** out) {
+    if (!e || !out || (n_rows && (!length || !offsets || !strands))) return fail(1, "engine, rows and out must be non-null");
+    *out = nullptr;
+    MMT_TRY
+    std::unique_ptr<mmt_merged> m(new mmt_merged());
+    mmt::MergedRows& R = m->rows;
+    hipStream_t st = e->e->stream();
+    MMT_HIP(hipSetDevice(e->e->device()));
+    R.n_rows = n_rows; R.n_docs = n_docs; R.thresh_len = 0;
+    R.d_length.ensure(n_rows + 1); R.d_offsets.ensure(n_rows * n_docs + 1); R.d_strands.ensure(n_rows * n_docs + 1);
+    R.d_thresh.ensure(1);
+    if (n_rows) {
+        MMT_HIP(hipMemcpyAsync(R.d_length.get(), length, n_rows * 4, hipMemcpyDeviceToDevice, st));
+        MMT_HIP(hipMemcpyAsync(R.d_offsets.get(), offsets, n_rows * n_docs * 8, hipMemcpyDeviceToDevice, st));
+        MMT_HIP(hipMemcpyAsync(R.d_strands.get(), strands, n_rows * n_docs, hipMemcpyDeviceToDevice, st));
+    }
+    MMT_HIP(hipStreamSynchronize(st));
+    R.on_host = false;
+    m->engine = e->e.get();
+    *out = m.release();
+    MMT_CATCH
+}
+// ---- collinear blocks (collinear.cpp) -------------------------------------------------------
+int mmt_merged_collinear(mmt_engine* e, mmt_merged* m, uint32_t max_break, int64_t min_singleton_length, uint64_t* n_blocks) {
+    if (!e || !m) return fail(1, "engine and merged rows must be non-null");
+    if (e->e.get() != m->engine) return fail(1, "the merged rows belong to another engine");
+    MMT_TRY
+    m->text.clear(); m->text_valid = false;
+    mmt::collinear_blocks(*e->e, m->rows, max_break, min_singleton_length, &m->coll);
+    if (n_blocks) *n_blocks = m->rows.n_blocks;
+    MMT_CATCH
+}
+int mmt_merged_blocks(const mmt_merged* m, uint32_t* lr) {
+    if (!m) return fail(1, "null");
+    if (!m->rows.has_blocks) return fail(3, "no collinear blocks attached: call mmt_merged_collinear first");
+    MMT_TRY
+    if (m->rows.n_blocks) {
+        if (!lr) throw std::invalid_argument("lr must hold 2 x n_blocks entries");
+        hipStream_t st = m->engine->stream();
+        MMT_HIP(hipSetDevice(m->engine->device()));
+        MMT_HIP(hipMemcpyAsync(lr, m->rows.d_blocks.get(), m->rows.n_blocks * 8, hipMemcpyDeviceToHost, st));
+        MMT_HIP(hipStreamSynchronize(st));
+    }
+    MMT_CATCH
+}
+int mmt_merged_blocks_device(const mmt_merged* m, const uint32_t** lr, const uint32_t** row_block) {
+    if (!m) return fail(1, "null");
+    if (!m->rows.has_blocks) return fail(3, "no collinear blocks attached: call mmt_merged_collinear first");
+    if (lr) *lr = m->rows.d_blocks.get();
+    if (row_block) *row_block = m->rows.d_row_block.get();
+    return 0;
+}
+int mmt_merged_collinear_stats(const mmt_merged* m, double out[12]) {
+    if (!m || !out) return fail(1, "null");
+    const mmt::CollinearStats& S = m->coll;
+    for (int i = 0; i < 5; i++) out[i] = S.ms[i];
+    out[5] = (double)S.rows_in; out[6] = (double)S.rows_kept; out[7] = (double)S.cols_sorted; out[8] = (double)S.cols_ascending;
+    out[9] = (double)S.batches; out[10] = (double)S.table_sorted; out[11] = (double)m->rows.n_blocks;
+    return 0;
 }
 int mmt_merged_sort_like_direct(mmt_engine* e, mmt_merged* m) {
     if (!e || !m) return fail(1, "null");

@@ -453,7 +453,11 @@ void sort_like_direct(Engine& e, MergedRows& m) {
     if (bad) throw std::runtime_error("anchor offset outside the anchor");
     m.d_length.swap(len2); m.d_offsets.swap(off2); m.d_strands.swap(st2);
     m.on_host = false;
+    m.has_blocks = false; m.n_blocks = 0;       // (blocks are row ranges of the order they were computed in)
 }
+
+// the fourth field of the text: the collinear block of every row, when blocks are attached (collinear.hpp)
+static const uint32_t* row_block(const MergedRows& m) { return m.has_blocks ? m.d_row_block.get() : nullptr; }
 
 // .mums bytes of the merged rows in HBM; returns their number
 static size_t format_merged_device(Engine& e, const MergedRows& m, DevBuf<char>& text) {
@@ -463,7 +467,7 @@ static size_t format_merged_device(Engine& e, const MergedRows& m, DevBuf<char>&
     MMT_HIP(hipSetDevice(e.device()));
     DevBuf<uint64_t> tlen, toff;
     tlen.ensure(n); toff.ensure(n);
-    mk::table_measure(m.d_length.get(), m.d_offsets.get(), (uint32_t)n, (uint32_t)m.n_docs, tlen.get(), st);
+    mk::table_measure(m.d_length.get(), m.d_offsets.get(), row_block(m), (uint32_t)n, (uint32_t)m.n_docs, tlen.get(), st);
     prims::exclusive_sum_u64(e.scratch(), tlen.get(), toff.get(), n, st);
     uint64_t last[2] = {0, 0};
     MMT_HIP(hipMemcpyAsync(&last[0], toff.get() + (n - 1), 8, hipMemcpyDeviceToHost, st));
@@ -471,8 +475,8 @@ static size_t format_merged_device(Engine& e, const MergedRows& m, DevBuf<char>&
     MMT_HIP(hipStreamSynchronize(st));
     const size_t bytes = (size_t)(last[0] + last[1]);
     text.ensure(bytes + 1);
-    mk::table_write(m.d_length.get(), m.d_offsets.get(), m.d_strands.get(), (uint32_t)n, (uint32_t)m.n_docs, toff.get(), 0,
-                    text.get(), st);
+    mk::table_write(m.d_length.get(), m.d_offsets.get(), m.d_strands.get(), row_block(m), (uint32_t)n, (uint32_t)m.n_docs,
+                    toff.get(), 0, text.get(), st);
     return bytes;
 }
 
@@ -521,7 +525,7 @@ void write_merged_text(Engine& e, const MergedRows& m, const std::string& path) 
     }
     DevBuf<uint64_t> tlen, toff;
     tlen.ensure(n + 1); toff.ensure(n + 1);
-    mk::table_measure(m.d_length.get(), m.d_offsets.get(), (uint32_t)n, (uint32_t)m.n_docs, tlen.get(), st);
+    mk::table_measure(m.d_length.get(), m.d_offsets.get(), row_block(m), (uint32_t)n, (uint32_t)m.n_docs, tlen.get(), st);
     MMT_HIP(hipMemsetAsync(tlen.get() + n, 0, 8, st));
     prims::exclusive_sum_u64(e.scratch(), tlen.get(), toff.get(), n + 1, st);     // toff[n] = all bytes
     std::vector<uint64_t> h_off(n + 1);
@@ -548,7 +552,7 @@ void write_merged_text(Engine& e, const MergedRows& m, const std::string& path) 
         const size_t r0 = cut[i], r1 = cut[i + 1];
         PieceWriter::Piece pc = writer.room(h_off[r1] - h_off[r0]);
         mk::table_write(m.d_length.get() + r0, m.d_offsets.get() + r0 * m.n_docs, m.d_strands.get() + r0 * m.n_docs,
-                        (uint32_t)(r1 - r0), (uint32_t)m.n_docs, toff.get() + r0, h_off[r0], d.get(), st);
+                        row_block(m) ? row_block(m) + r0 : nullptr, (uint32_t)(r1 - r0), (uint32_t)m.n_docs, toff.get() + r0, h_off[r0], d.get(), st);
         MMT_HIP(hipMemcpyAsync(pc.p, d.get(), pc.n, hipMemcpyDeviceToHost, st));
         MMT_HIP(hipStreamSynchronize(st));
         writer.push(pc);

@@ -229,28 +229,36 @@ __device__ __forceinline__ uint32_t cell_width(int64_t o) {
     return o < 0 ? 1u + ndigits((uint64_t)(-o)) : ndigits((uint64_t)o);
 }
 
-__global__ void k_table_measure(const uint32_t* __restrict__ len, const int64_t* __restrict__ off, uint32_t n,
-                                uint32_t n_docs, uint64_t* __restrict__ text_len) {
+// the optional fourth field (collinear block of the row, mumemto/utils.py:637-653): \t + its number, or \t- for none
+__device__ __forceinline__ uint32_t block_width(const uint32_t* __restrict__ block, uint64_t r) {
+    return !block ? 0u : 1u + (block[r] == 0xffffffffu ? 1u : ndigits(block[r]));
+}
+
+__global__ void k_table_measure(const uint32_t* __restrict__ len, const int64_t* __restrict__ off,
+                                const uint32_t* __restrict__ block, uint32_t n, uint32_t n_docs,
+                                uint64_t* __restrict__ text_len) {
     const uint64_t r = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint32_t lane = threadIdx.x & 63;
     if (r >= n) return;
     uint32_t w = 0;
     for (uint32_t d = lane; d < n_docs; d += 64) w += cell_width(off[r * n_docs + d]);
     w = wave_sum(w);
-    // LEN \t offs(N-1 commas) \t strands(N chars, N-1 commas) \n
-    if (lane == 0) text_len[r] = (uint64_t)ndigits(len[r]) + 1 + w + (n_docs - 1) + 1 + n_docs + (n_docs - 1) + 1;
+    // LEN \t offs(N-1 commas) \t strands(N chars, N-1 commas) [\t block] \n
+    if (lane == 0)
+        text_len[r] = (uint64_t)ndigits(len[r]) + 1 + w + (n_docs - 1) + 1 + n_docs + (n_docs - 1) + block_width(block, r) + 1;
 }
-void table_measure(const uint32_t* len, const int64_t* off, uint32_t n, uint32_t n_docs, uint64_t* text_len,
-                   hipStream_t s) {
+void table_measure(const uint32_t* len, const int64_t* off, const uint32_t* block, uint32_t n, uint32_t n_docs,
+                   uint64_t* text_len, hipStream_t s) {
     if (!n) return;
-    hipLaunchKernelGGL(k_table_measure, dim3(grid_for((uint64_t)n * 64, 256)), dim3(256), 0, s, len, off, n, n_docs,
+    hipLaunchKernelGGL(k_table_measure, dim3(grid_for((uint64_t)n * 64, 256)), dim3(256), 0, s, len, off, block, n, n_docs,
                        text_len);
     MMT_HIP(hipGetLastError());
 }
 
 __global__ void k_table_write(const uint32_t* __restrict__ len, const int64_t* __restrict__ off,
-                              const uint8_t* __restrict__ st, uint32_t n, uint32_t n_docs,
-                              const uint64_t* __restrict__ text_off, uint64_t text_base, char* __restrict__ text) {
+                              const uint8_t* __restrict__ st, const uint32_t* __restrict__ block, uint32_t n,
+                              uint32_t n_docs, const uint64_t* __restrict__ text_off, uint64_t text_base,
+                              char* __restrict__ text) {
     const uint64_t r = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint32_t lane = threadIdx.x & 63;
     if (r >= n) return;
@@ -277,12 +285,21 @@ __global__ void k_table_write(const uint32_t* __restrict__ len, const int64_t* _
         t[cur + 2 * d] = st[r * n_docs + d] ? '+' : '-';
         if (d + 1 < n_docs) t[cur + 2 * d + 1] = ',';
     }
-    if (lane == 0) t[cur + 2 * n_docs - 1] = '\n';
+    if (lane == 0) {
+        cur += 2 * n_docs - 1;
+        if (block) {
+            t[cur++] = '\t';
+            const uint32_t b = block[r];
+            if (b == 0xffffffffu) t[cur++] = '-';
+            else { const uint32_t nb = ndigits(b); put_uint(t + cur, b, nb); cur += nb; }
+        }
+        t[cur] = '\n';
+    }
 }
-void table_write(const uint32_t* len, const int64_t* off, const uint8_t* st, uint32_t n, uint32_t n_docs,
+void table_write(const uint32_t* len, const int64_t* off, const uint8_t* st, const uint32_t* block, uint32_t n, uint32_t n_docs,
                  const uint64_t* text_off, uint64_t text_base, char* text, hipStream_t s) {
     if (!n) return;
-    hipLaunchKernelGGL(k_table_write, dim3(grid_for((uint64_t)n * 64, 256)), dim3(256), 0, s, len, off, st, n, n_docs,
+    hipLaunchKernelGGL(k_table_write, dim3(grid_for((uint64_t)n * 64, 256)), dim3(256), 0, s, len, off, st, block, n, n_docs,
                        text_off, text_base, text);
     MMT_HIP(hipGetLastError());
 }

@@ -53,10 +53,11 @@ void rank_keys(const int64_t* off, uint32_t n, uint32_t n_docs, const uint32_t* 
                uint32_t* keys, uint32_t* vals, uint32_t* bad, hipStream_t s);
 void rank_keys64(const int64_t* off, uint32_t n, uint32_t n_docs, const uint64_t* isa, uint64_t anchor_len,
                  uint64_t* keys, uint32_t* vals, uint32_t* bad, hipStream_t s);
-// mumsio::serialize_mum (include/mumsio.hpp:311-320): LEN \t offsets \t strands \n; one wave per row
-void table_measure(const uint32_t* len, const int64_t* off, uint32_t n, uint32_t n_docs, uint64_t* text_len,
-                   hipStream_t s);
-void table_write(const uint32_t* len, const int64_t* off, const uint8_t* st, uint32_t n, uint32_t n_docs,
+// mumsio::serialize_mum (include/mumsio.hpp:311-320): LEN \t offsets \t strands \n; one wave per row.  block (may be null):
+// the collinear block of every row, written as a fourth field \t NUMBER, or \t - for 0xFFFFFFFF (mumemto/utils.py:637-653)
+void table_measure(const uint32_t* len, const int64_t* off, const uint32_t* block, uint32_t n, uint32_t n_docs,
+                   uint64_t* text_len, hipStream_t s);
+void table_write(const uint32_t* len, const int64_t* off, const uint8_t* st, const uint32_t* block, uint32_t n, uint32_t n_docs,
                  const uint64_t* text_off, uint64_t text_base, char* text, hipStream_t s);   // row r -> text + text_off[r] - text_base
 
 }}  // namespace mmt::mk

@@ -20,6 +20,11 @@ struct MergedRows {
     std::vector<int64_t> offsets;
     std::vector<uint8_t> strands;
     std::vector<uint16_t> thresh;
+    // collinear blocks (collinear.hpp), attached by collinear_blocks(): the table above is then the filtered, sorted one
+    bool has_blocks = false;
+    size_t n_blocks = 0;
+    DevBuf<uint32_t> d_row_block;   // n_rows: block of the row, 0xFFFFFFFF = none
+    DevBuf<uint32_t> d_blocks;      // n_blocks x (first row, last row)
 
     MergedRows() = default;
     MergedRows(MergedRows&& o) noexcept { *this = std::move(o); }
@@ -28,6 +33,8 @@ struct MergedRows {
         d_length.swap(o.d_length); d_offsets.swap(o.d_offsets); d_strands.swap(o.d_strands); d_thresh.swap(o.d_thresh);
         length = std::move(o.length); offsets = std::move(o.offsets); strands = std::move(o.strands);
         thresh = std::move(o.thresh);
+        has_blocks = o.has_blocks; n_blocks = o.n_blocks;
+        d_row_block.swap(o.d_row_block); d_blocks.swap(o.d_blocks);
         return *this;
     }
 };
