@@ -35,9 +35,7 @@ std::unique_ptr<mmt::Engine> g_engine;
 
 mmt::Engine& shared_engine() {
     if (!g_engine) {
-        int dev = 0;
-        if (const char* s = std::getenv("MUMEMTO_DEVICE")) dev = std::atoi(s);
-        g_engine.reset(new mmt::Engine(dev, nullptr));
+        g_engine.reset(new mmt::Engine(mmt::env_device(), nullptr));
     }
     return *g_engine;
 }
@@ -308,7 +306,7 @@ int mmt_engine_run_files(mmt_engine* e, const char* const* paths, size_t n_paths
     mmt::ReadHooks hooks;
     hooks.layout = [&](const uint8_t* arena, size_t bytes, const std::vector<size_t>& slot, bool all_in_arena) {
         const uint64_t bound = 2 * ((uint64_t)bytes + slot.size());               // text characters at most
-        if (!all_in_arena || std::getenv("MUMEMTO_NO_UPLOAD_OVERLAP") || slot.size() < 2) return;
+        if (!all_in_arena || sw::on(sw::MUMEMTO_NO_UPLOAD_OVERLAP) || slot.size() < 2) return;
         e->e->forget_last_run();
         if (bound > (max_text_chars ? max_text_chars : e->e->auto_max_text())) return;
         uint8_t* dev = e->e->begin_input_slots(bytes);

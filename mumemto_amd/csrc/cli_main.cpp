@@ -41,8 +41,7 @@ static const auto g_start = std::chrono::steady_clock::now();
 static double secs_since(std::chrono::steady_clock::time_point t0);
 // MUMEMTO_TIMING=1: wall-clock marks (seconds since the process started) on stderr
 static void mark(const char* what) {
-    static const bool on = std::getenv("MUMEMTO_TIMING") != nullptr;
-    if (on) std::fprintf(stderr, "[timing] %8.3f  %s\n", secs_since(g_start), what);
+    if (sw::on(sw::MUMEMTO_TIMING)) std::fprintf(stderr, "[timing] %8.3f  %s\n", secs_since(g_start), what);
 }
 static double secs_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -188,9 +187,9 @@ static int launch_ranks(int argc, char** argv, const BuildOptions& o) {
             std::vector<char*> av;
             for (auto& s : args) av.push_back(const_cast<char*>(s.c_str()));
             av.push_back(nullptr);
-            if (!std::getenv("MUMEMTO_SHARE_DEVICE")) setenv("MUMEMTO_DEVICE", std::to_string(r).c_str(), 1);
+            if (!sw::on(sw::MUMEMTO_SHARE_DEVICE)) setenv("MUMEMTO_DEVICE", std::to_string(r).c_str(), 1);
             // the ranks share the node's CPUs (a container's quota): every reader takes its part
-            if (!std::getenv("MUMEMTO_READ_THREADS"))
+            if (!sw::is_set(sw::MUMEMTO_READ_THREADS))
                 setenv("MUMEMTO_READ_THREADS", std::to_string(std::max<size_t>(2, reader_threads() / (size_t)o.gpus)).c_str(), 1);
             execv("/proc/self/exe", av.data());
             std::_Exit(127);
@@ -272,7 +271,7 @@ static uint64_t host_memory_available() {
     return avail;
 }
 static bool want_streamed_input(const std::vector<std::string>& inputs, size_t copies) {       // copies: processes that each hold it
-    if (const char* e = std::getenv("MUMEMTO_STREAM_INPUT")) return std::atoi(e) != 0;
+    if (sw::is_set(sw::MUMEMTO_STREAM_INPUT)) return sw::on(sw::MUMEMTO_STREAM_INPUT);
     uint64_t bound = 0;                                      // bases at most: a compressed file counted four times
     for (const auto& p : inputs) {
         std::error_code ec;
@@ -395,8 +394,8 @@ static int run_streamed(BuildOptions& o, const std::vector<std::string>& inputs,
     std::unique_ptr<Engine> engine;
     std::exception_ptr engine_error;
     std::thread engine_init([&]() {
-        if (std::getenv("MUMEMTO_DRY_RUN")) return;
-        try { engine.reset(new Engine(std::getenv("MUMEMTO_DEVICE") ? std::atoi(std::getenv("MUMEMTO_DEVICE")) : 0, nullptr)); }
+        if (sw::on(sw::MUMEMTO_DRY_RUN)) return;
+        try { engine.reset(new Engine(env_device(), nullptr)); }
         catch (...) { engine_error = std::current_exception(); }
     });
     struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } engine_joiner{engine_init};
@@ -408,7 +407,7 @@ static int run_streamed(BuildOptions& o, const std::vector<std::string>& inputs,
     write_lengths_file(o.output_prefix, in.docs);
     uint64_t n_bases = 0, text_chars = 0;
     for (uint64_t l : in.len) { n_bases += l; text_chars += (o.use_rcomp ? 2 : 1) * (l + 1); }
-    if (std::getenv("MUMEMTO_DRY_RUN")) {          // host-side checks only: every document through the supplier, in order
+    if (sw::on(sw::MUMEMTO_DRY_RUN)) {          // host-side checks only: every document through the supplier, in order
         engine_init.join();
         uint64_t h = 1469598103934665603ull;
         std::vector<uint8_t> dst;
@@ -471,7 +470,7 @@ static int run_streamed(BuildOptions& o, const std::vector<std::string>& inputs,
     std::fprintf(stderr, "GPU stages (ms): text %.2f | suffix sort %.2f (stream windows %.2f of it) | lcp+bwt %.2f | scan %.2f | verify %.2f | rows %.2f\n\n",
                  ms[0], ms[1], ms[6], ms[2], ms[3], ms[4], ms[5]);
     std::fflush(stdout); std::fflush(stderr);
-    if (!std::getenv("MUMEMTO_FULL_TEARDOWN")) std::_Exit(0);
+    if (!sw::on(sw::MUMEMTO_FULL_TEARDOWN)) std::_Exit(0);
     return 0;
 }
 
@@ -502,8 +501,8 @@ static int run_rank(BuildOptions& o) {
     // much for the host, as long as it runs as ONE text: anchor partitions inside a rank read their documents again and
     // again and keep them resident)
     bool streamed = want_streamed_input(mine, (size_t)world);
-    const bool pieces = !strict && (std::getenv("MUMEMTO_RANK_PIECES") ? std::atoi(std::getenv("MUMEMTO_RANK_PIECES")) != 0 : streamed);
-    Engine eng(std::getenv("MUMEMTO_DEVICE") ? std::atoi(std::getenv("MUMEMTO_DEVICE")) : 0, nullptr);
+    const bool pieces = !strict && (sw::is_set(sw::MUMEMTO_RANK_PIECES) ? sw::on(sw::MUMEMTO_RANK_PIECES) : streamed);
+    Engine eng(env_device(), nullptr);
     HostArena arena;
     HostDocs hd;
     std::vector<FastaDoc> docs;
@@ -514,7 +513,7 @@ static int run_rank(BuildOptions& o) {
         in.paths = mine; empty = in.measure(); docs = in.docs; hd.len = in.len;
         uint64_t chars = 0;
         for (uint64_t l : in.len) chars += (o.use_rcomp ? 2 : 1) * (l + 1);
-        if (strict && empty < 0 && (chars > eng.auto_max_text() || std::getenv("MUMEMTO_MAX_TEXT") || std::getenv("MMT_MAX_TEXT"))) {
+        if (strict && empty < 0 && (chars > eng.auto_max_text() || sw::is_set(sw::MUMEMTO_MAX_TEXT) || sw::is_set(sw::MMT_MAX_TEXT))) {
             streamed = false; docs.clear(); hd.len.clear();
         }
     }
@@ -596,7 +595,7 @@ int main(int argc, char** argv) {
         if (o.help) { std::fputs(usage_text().c_str(), stderr); return 0; }
         if (o.gpus < 1) throw CliError{"--gpus needs a positive number", 1};
         if (o.rank >= 0) return run_rank(o);
-        if (o.gpus > 1 || std::getenv("MUMEMTO_FORCE_RANKS")) { (void)o.validate(); return launch_ranks(argc, argv, o); }
+        if (o.gpus > 1 || sw::on(sw::MUMEMTO_FORCE_RANKS)) { (void)o.validate(); return launch_ranks(argc, argv, o); }
         const bool mum_mode = o.validate();
         const bool checkpoint = o.from_parse_flag || o.arrays_in_flag;
         std::vector<uint64_t> doc_len;
@@ -608,7 +607,7 @@ int main(int argc, char** argv) {
         if (!checkpoint && want_streamed_input(inputs, 1)) return run_streamed(o, inputs, mum_mode);
         auto t0 = std::chrono::steady_clock::now();
         // the HIP runtime comes up (device, stream, code objects) while the host threads read the inputs
-        const bool dry_run = std::getenv("MUMEMTO_DRY_RUN") != nullptr;
+        const bool dry_run = sw::on(sw::MUMEMTO_DRY_RUN);
         std::unique_ptr<Engine> engine;
         std::exception_ptr engine_error;
         std::thread engine_init;
@@ -619,7 +618,7 @@ int main(int argc, char** argv) {
         // the inputs are on their way, before any kernel runs.  Chunks mapped beside running work each waited ~30 ms for it:
         // 0.04 - 0.10 s of a 1.9 s process, and never the same twice.  MUMEMTO_NO_PREMAP switches it off.)
         size_t premap_bytes = 0, slots_bound = 0;
-        if (!dry_run && !checkpoint && !std::getenv("MUMEMTO_NO_PREMAP")) {
+        if (!dry_run && !checkpoint && !sw::on(sw::MUMEMTO_NO_PREMAP)) {
             double file_bytes = 0;
             for (const auto& f : inputs) { std::error_code ec; const auto sz = std::filesystem::file_size(f, ec); if (!ec) file_bytes += (double)sz; }
             if (3.0 * 2.0 * file_bytes + 24.0 * 1073741824.0 <= 200.0 * 1073741824.0) {
@@ -631,7 +630,7 @@ int main(int argc, char** argv) {
         }
         if (!dry_run)
             engine_init = std::thread([&]() {
-                try { engine.reset(new Engine(std::getenv("MUMEMTO_DEVICE") ? std::atoi(std::getenv("MUMEMTO_DEVICE")) : 0, nullptr)); }
+                try { engine.reset(new Engine(env_device(), nullptr)); }
                 catch (...) { engine_error = std::current_exception(); }
                 try { if (engine && slots_bound && slots_bound * 2 <= engine->auto_max_text()) (void)engine->begin_input_slots(slots_bound); } catch (...) {}
                 engine_up.set_value();
@@ -651,7 +650,7 @@ int main(int argc, char** argv) {
         } up;
         ReadHooks hooks;
         hooks.layout = [&](const uint8_t* arena_p, size_t bytes, const std::vector<size_t>& slot, bool all_in_arena) {
-            if (dry_run || !all_in_arena || std::getenv("MUMEMTO_NO_UPLOAD_OVERLAP") || slot.size() < 2) return;
+            if (dry_run || !all_in_arena || sw::on(sw::MUMEMTO_NO_UPLOAD_OVERLAP) || slot.size() < 2) return;
             up.slot = slot; up.on = true;
             up.thread = std::thread([&up, &engine, &engine_error, engine_ready, arena_p, bytes]() {
                 try {
@@ -702,15 +701,15 @@ int main(int argc, char** argv) {
             std::once_flag once; uint8_t* dev = nullptr; int device = 0;
         } cu;
         // (MUMEMTO_INPUT_CHUNK_MB: tuning aid; page-locked memory costs 0.19 s per GB when it is made and 0.13 s per GB at the exit)
-        const size_t CHUNK = (size_t)(std::getenv("MUMEMTO_INPUT_CHUNK_MB") ? std::max(1, std::atoi(std::getenv("MUMEMTO_INPUT_CHUNK_MB"))) : 8) << 20;
+        const size_t CHUNK = (size_t)std::max(1, sw::num(sw::MUMEMTO_INPUT_CHUNK_MB, 8)) << 20;
         // (MUMEMTO_DRY_RUN_CHUNK=<bytes>, with MUMEMTO_DRY_RUN: the chunked reader into host vectors, chunks of that many bytes
         // -- the host-side test of the chunk logic, tests/test_cli_host.py)
-        const size_t dry_chunk = dry_run && std::getenv("MUMEMTO_DRY_RUN_CHUNK") ? (size_t)std::max(1, std::atoi(std::getenv("MUMEMTO_DRY_RUN_CHUNK"))) : 0;
+        const size_t dry_chunk = dry_run && sw::is_set(sw::MUMEMTO_DRY_RUN_CHUNK) ? (size_t)std::max(1, sw::num(sw::MUMEMTO_DRY_RUN_CHUNK, 0)) : 0;
         std::vector<std::vector<uint8_t>> dry_docs;
         hooks.plan_chunks = [&](size_t bytes, const std::vector<size_t>& slot, bool all_plain) {
             if (dry_chunk && all_plain) { dry_docs.assign(slot.size() - 1, std::vector<uint8_t>()); cu.on = true; return true; }
-            if (dry_run || !all_plain || slot.size() < 2 || std::getenv("MUMEMTO_NO_UPLOAD_OVERLAP") ||
-                std::getenv("MUMEMTO_NO_CHUNKED_INPUT") || std::getenv("MUMEMTO_KEEP_HOST_INPUT")) return false;
+            if (dry_run || !all_plain || slot.size() < 2 || sw::on(sw::MUMEMTO_NO_UPLOAD_OVERLAP) ||
+                sw::on(sw::MUMEMTO_NO_CHUNKED_INPUT) || sw::on(sw::MUMEMTO_KEEP_HOST_INPUT)) return false;
             // (only collections that will clearly run as one suffix array on a device of this class: Engine::auto_max_text's
             // formula with 200 GB in place of the free memory nobody has asked the driver for yet)
             if (3.0 * 2.0 * (double)(bytes + slot.size()) + 24.0 * 1073741824.0 > 200.0 * 1073741824.0) return false;
@@ -841,11 +840,11 @@ int main(int argc, char** argv) {
         // its mapped device memory -- 123 or 79 GB mapped at exit: the same 0.45 s; a bare HIP process 0.08 s; 100 GB of hipMalloc
         // 0.06 s -- but page-locked HOST memory, 0.13 s per GB: the sink's blocks are 64 MB now.  Handing the heap's free top back
         // early therefore buys nothing and costs the run ~0.08 s: opt-in)
-        eng.set_one_shot(std::getenv("MUMEMTO_EARLY_UNMAP") != nullptr);
+        eng.set_one_shot(sw::on(sw::MUMEMTO_EARLY_UNMAP));
         // one suffix array while the text fits the device (40-bit positions beyond 2^32 characters); beyond that --
         // or beyond MUMEMTO_MAX_TEXT characters -- strict multi-MUMs run as anchor partitions + merge on this GPU
         // (the same estimate as the library: Engine::auto_max_text, MUMEMTO_MAX_TEXT overrides both)
-        const bool explicit_limit = std::getenv("MUMEMTO_MAX_TEXT") || std::getenv("MMT_MAX_TEXT");
+        const bool explicit_limit = sw::is_set(sw::MUMEMTO_MAX_TEXT) || sw::is_set(sw::MMT_MAX_TEXT);
         const uint64_t max_text = eng.auto_max_text();
         const bool strict_mode = mum_mode && (o.num_distinct_docs == 0 || (size_t)o.num_distinct_docs == doc_len.size());
         // modes without a partition merge are tried as one run whatever the estimate says, like the library does
@@ -963,10 +962,10 @@ int main(int argc, char** argv) {
         }
         mark("outputs written");
         const pool::Stats heap = pool::stats(eng.device());
-        if (std::getenv("MUMEMTO_TIMING"))
+        if (sw::on(sw::MUMEMTO_TIMING))
             std::fprintf(stderr, "[timing] device heap: %.2f GB live at the peak, %.2f GB mapped, %.3f s mapping it\n",
                          heap.peak / 1073741824.0, heap.mapped / 1073741824.0, heap.map_seconds);
-        if (const char* sp = std::getenv("MUMEMTO_STATS")) {       // one JSON object for bench.py
+        if (const char* sp = sw::text(sw::MUMEMTO_STATS)) {       // one JSON object for bench.py
             const float* sm = eng.stage_ms();
             const float* pm = eng.pfp_state().ms;
             std::ofstream js(sp);
@@ -989,7 +988,7 @@ int main(int argc, char** argv) {
         // Everything is on disk: leave without unloading the HIP runtime and freeing gigabytes of HBM buffer by buffer
         // (the driver reclaims them with the process).  MUMEMTO_FULL_TEARDOWN=1 keeps the orderly exit, which
         // profilers that flush at exit need.
-        if (!std::getenv("MUMEMTO_FULL_TEARDOWN")) {
+        if (!sw::on(sw::MUMEMTO_FULL_TEARDOWN)) {
             std::fflush(stdout); std::fflush(stderr);
             std::_Exit(0);
         }

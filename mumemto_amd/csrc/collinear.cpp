@@ -123,7 +123,7 @@ void collinear_blocks(Engine& e, MergedRows& m, uint32_t max_break, int64_t min_
         size_t batch = nd;
         const size_t avail = pool::available(e.device()) / 2, one_sort = (size_t)n * 24;
         if ((size_t)nd * n * 8 + one_sort > avail) batch = avail > one_sort ? (avail - one_sort) / ((size_t)n * 8) : 1;
-        if (const char* c = std::getenv("MMT_COLLINEAR_BATCH")) batch = std::strtoull(c, nullptr, 10);
+        batch = (size_t)sw::num(sw::MMT_COLLINEAR_BATCH, batch);
         batch = std::min<size_t>(std::max<size_t>(batch, 1), nd);
         keys.ensure(batch * n);
         // per column: 1 = not ascending; behind them, 8-byte aligned, the 64-bit OR of the starts

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "pool.hpp"
+#include "switches.hpp"
 
 namespace mmt {
 
@@ -39,8 +40,18 @@ struct DevBytes {
     static size_t& live() { static size_t v = 0; return v; }
     static size_t& peak() { static size_t v = 0; return v; }
     static double& seconds() { static double v = 0; return v; }
-    static bool log() { static const bool on = std::getenv("MUMEMTO_ALLOC_LOG") != nullptr; return on; }
+    static bool log() { return sw::on(sw::MUMEMTO_ALLOC_LOG); }
 };
+
+// MMT_MEM_TRACE=1: live / peak bytes of the device heap at the stage boundaries (stderr)
+inline void mem_mark(int device, const char* what) {
+    if (!sw::on(sw::MMT_MEM_TRACE)) return;
+    const pool::Stats s = pool::stats(device);
+    std::fprintf(stderr, "[mem] %-28s live %7.2f GB  peak %7.2f GB  mapped %7.2f GB\n", what, s.live / 1e9, s.peak / 1e9, s.mapped / 1e9);
+}
+
+// MUMEMTO_DEVICE: the device of the tools and of the host-string ABI
+inline int env_device() { return sw::num(sw::MUMEMTO_DEVICE, 0); }
 
 // Device allocation that only grows (steps of the hot path are re-run by the
 // bench with the same sizes), taken from the per-device heap of pool.hpp.

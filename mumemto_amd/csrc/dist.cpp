@@ -52,7 +52,7 @@ Rccl& rccl() {
     void* h = nullptr;
     // MUMEMTO_RCCL_LIB: this library and no other (the tests' transport double, tests/fake_rccl: ranks = processes that
     // share one GPU -- the only way the exchange below runs with more than one rank on a one-GPU box)
-    if (const char* path = std::getenv("MUMEMTO_RCCL_LIB")) {
+    if (const char* path = sw::text(sw::MUMEMTO_RCCL_LIB)) {
         h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
         if (!h) throw std::runtime_error(std::string("cannot load MUMEMTO_RCCL_LIB: ") + dlerror());
     }
@@ -100,8 +100,7 @@ void check(ncclResult_t e, const char* what) {
 // arrive different, without an error.  Rounds 4 and 5 cut at 2^30 ELEMENTS (4 - 8 GiB a piece).  Half a gibibyte leaves a margin;
 // two dozen pieces of a 12 GB column cost nothing inside a group.
 static size_t rccl_chunk_elements(size_t width) {
-    static const size_t env = [] { const char* e = std::getenv("MUMEMTO_RCCL_CHUNK"); return e ? (size_t)std::strtoull(e, nullptr, 10) : (size_t)0; }();
-    if (env) return env;
+    if (const size_t env = (size_t)sw::num(sw::MUMEMTO_RCCL_CHUNK, 0)) return env;
     return ((size_t)1 << 29) / width;
 }
 template <typename T>
@@ -201,7 +200,7 @@ enum Table { T_LENGTHS = 0, T_OFFSETS, T_STRANDS, T_THRESHOLDS, T_TEXT, T_DIGEST
 static const char* const kTableName[] = {"lengths", "offsets", "strands", "thresholds", "text", "digests"};
 
 static bool verify_wanted() {
-    const char* e = std::getenv("MUMEMTO_EXCHANGE_VERIFY");
+    const char* e = sw::text(sw::MUMEMTO_EXCHANGE_VERIFY);
     return !(e && std::string(e) == "0");
 }
 
@@ -329,7 +328,7 @@ static MergedRows merge_routed(Comm& c, uint32_t min_len, bool* is_root, int rou
     const HostRows& R = e.rows_meta();
     if (!R.mum_mode || !e.thresh_len()) throw std::runtime_error("the exchange needs a multi-MUM run with merge metadata");
     if (route < 0) {
-        const char* env = std::getenv("MUMEMTO_RANGE_FOLD");
+        const char* env = sw::text(sw::MUMEMTO_RANGE_FOLD);
         route = env ? (std::string(env) == "1" ? 1 : 0) : (c.world >= 4 ? 1 : 0);
     }
     const uint32_t* my_len; const int64_t* my_off; const uint8_t* my_st;

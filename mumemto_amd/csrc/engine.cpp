@@ -18,12 +18,11 @@ static int bit_width_u64(uint64_t v) { int b = 0; while (v) { b++; v >>= 1; } re
 // (64 MB: page-locking costs 0.19 s per GB when a block is made and 0.13 s per GB when the process ends -- four blocks of
 // 256 MB were a quarter of a second of the bench workload's 2.2 s from process start to exit)
 static size_t sink_block_bytes() {
-    const char* mb = std::getenv("MMT_SINK_BLOCK_MB");
-    return (size_t)(mb ? std::max(1, std::atoi(mb)) : 64) << 20;
+    return (size_t)std::max(1, sw::num(sw::MMT_SINK_BLOCK_MB, 64)) << 20;
 }
 
 Engine::Engine(int device, hipStream_t stream) : device_(device), stream_(stream), sink_writer_(sink_block_bytes(), 4) {
-    lean_ = std::getenv("MUMEMTO_LEAN") != nullptr;      // tests: stage scratch is released between the stages
+    lean_ = sw::on(sw::MUMEMTO_LEAN);      // tests: stage scratch is released between the stages
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
     if (e != hipSuccess || count == 0)
@@ -126,7 +125,7 @@ void Engine::layout_docs(bool revcomp) {
     if (n_ >= (1ull << 40))
         throw std::runtime_error("text of " + std::to_string(n_) + " characters exceeds 40-bit positions");
     // MMT_FORCE_WIDE: the 40-bit code path on small inputs (tests)
-    wide_ = n_ >= NARROW_LIMIT || std::getenv("MMT_FORCE_WIDE") != nullptr;
+    wide_ = n_ >= NARROW_LIMIT || sw::on(sw::MMT_FORCE_WIDE);
     d_doc_start_.ensure(N + 1);
     MMT_HIP(hipMemcpyAsync(d_doc_start_.get(), doc_start_.data(), (N + 1) * 8, hipMemcpyHostToDevice, stream_));
 }
@@ -203,7 +202,7 @@ TextRef Engine::text_ref() const {
 bool Engine::want_packed_text() const { return want_packed_text_of(n_); }
 // (the same predicate says whether the raw bases of a host-fed run go through staging buffers: partitioned.cpp)
 bool Engine::want_packed_text_of(uint64_t n, bool by_size_only) const {
-    if (const char* c = std::getenv("MMT_PACKED_TEXT")) { if (!by_size_only) return std::atoi(c) != 0; }
+    if (sw::is_set(sw::MMT_PACKED_TEXT) && !by_size_only) return sw::on(sw::MMT_PACKED_TEXT);
     // A text below 2^32 characters is never packed for want of room: on a small or busy device (less than ~27 GB free) the
     // formula below packed every text, a few kilobases too, and sent it to the bucket-wise producer with 256 MB of event
     // buffers and row discard -- such a device runs small collections normally or fails for what really does not fit.
@@ -410,7 +409,7 @@ void Engine::lcp_bwt() {
     d_plcp_a_.ensure(n); d_count_.ensure(8);
     const size_t rec = k::long_lcp_record_bytes(wide_) + 4;     // one record + one index for the second tier
     uint64_t cap64 = std::max<uint64_t>(d_long_.size() / rec, n / 256 + 4096);
-    if (const char* c = std::getenv("MMT_LONG_CAP")) cap64 = (uint64_t)std::max(1, std::atoi(c));   // tests: force the rerun
+    if (sw::is_set(sw::MMT_LONG_CAP)) cap64 = (uint64_t)std::max(1, sw::num(sw::MMT_LONG_CAP, 0));   // tests: force the rerun
     uint32_t cap = (uint32_t)std::min<uint64_t>(cap64, 0x7fffffffull);
     for (int attempt = 0; attempt < 2; attempt++) {
         d_long_.ensure((size_t)cap * rec);
@@ -419,7 +418,7 @@ void Engine::lcp_bwt() {
         uint32_t found = 0;
         MMT_HIP(hipMemcpyAsync(&found, d_count_.get() + 2, 4, hipMemcpyDeviceToHost, stream_));
         MMT_HIP(hipStreamSynchronize(stream_));
-        if (std::getenv("MMT_LCP_STATS")) std::fprintf(stderr, "[lcp] %u matches beyond 192 characters (list capacity %u)\n", found, cap);
+        if (sw::on(sw::MMT_LCP_STATS)) std::fprintf(stderr, "[lcp] %u matches beyond 192 characters (list capacity %u)\n", found, cap);
         if (found <= cap) {
             k::long_lcp(text_ptr(), n, wide_, d_long_.get(), found, d_plcp_a_.get(),
                         reinterpret_cast<uint32_t*>(d_long_.get() + (size_t)cap * (rec - 4)), d_count_.get() + 3, stream_);
@@ -739,7 +738,7 @@ void Engine::scan(const mmt_params& p) {
     const bool whole_lcp = lcp_whole_ && preset_ == 2;
     uint64_t range = n;
     if (wide_ || n >= 0xffffe000ull) range = 1ull << 28;
-    if (const char* c = std::getenv("MMT_SCAN_RANGE")) range = std::max<uint64_t>(1, std::strtoull(c, nullptr, 10));
+    if (sw::is_set(sw::MMT_SCAN_RANGE)) range = std::max<uint64_t>(1, sw::num(sw::MMT_SCAN_RANGE, 0));
     range = (range + ALIGN_R - 1) / ALIGN_R * ALIGN_R;
     uint64_t shard_lo = 0, shard_hi = n;
     if (shard_count_ > 1) {
@@ -903,18 +902,18 @@ Engine::RowsFormat Engine::format_rows(const k::Row* rows_abs, const k::Row* row
 void Engine::sink_open() {
     sink_written_path_.clear();
     sink_total_rows_ = 0;
-    if (sink_path_.empty() || std::getenv("MUMEMTO_NO_TEXT_SINK")) return;
+    if (sink_path_.empty() || sw::on(sw::MUMEMTO_NO_TEXT_SINK)) return;
     // Rows that have been written need not stay: with a sink, a run whose accepted rows would not fit the device next to
     // its text keeps nothing of a window once its bytes are on their way (BASELINE configs[4]: a rank's rows carry ~94
     // occurrences each -- tens of GB of suffix-array entries, offsets and text).  Such a run answers only for the file and
     // the number of rows.  MMT_SINK_DISCARD=0 / 1 overrides (tests).
     sink_discard_ = sink_force_discard_ ||
                     (!sink_keep_rows_ &&
-                     (std::getenv("MMT_SINK_DISCARD") ? std::atoi(std::getenv("MMT_SINK_DISCARD")) != 0 : (packed_ || n_ >= (1ull << 37))));
+                     (sw::is_set(sw::MMT_SINK_DISCARD) ? sw::on(sw::MMT_SINK_DISCARD) : (packed_ || n_ >= (1ull << 37))));
     if (!rows_.mum_mode && !sink_discard_) return;          // (a MEM run that keeps its rows writes its file at the end, as before)
     // ("/dev/null": the bytes are formatted, copied out, digested and dropped -- a full-size test run whose 66 GB of rows the
     // box has no room for)
-    sink_writer_.open(sink_path_, device_, std::getenv("MMT_SINK_DIGEST") != nullptr);
+    sink_writer_.open(sink_path_, device_, sw::on(sw::MMT_SINK_DIGEST));
     sink_rows_done_ = 0;
     sink_pieces_ = 0;
     if (!sink_stream_) {
@@ -1209,7 +1208,7 @@ void Engine::run(const mmt_params& p) {
             // bench, 3x at 0.1 % divergence), unless the text holds bytes the parse reserves (<= 0x02) or there are
             // too few documents for the dictionary to be much smaller than the text (measured, 1 % divergence:
             // 3 x 4.6 Mbp 8.6 vs 12.7 ms, 4 x 30 Mbp 80 vs 108 ms for the direct sort; even at 6 documents)
-            const char* env = std::getenv("MUMEMTO_PRODUCER");      // "direct" | "pfp" | "guided" override
+            const char* env = sw::text(sw::MUMEMTO_PRODUCER);      // "direct" | "pfp" | "guided" override
             const bool forced_pfp = env && std::string(env) == "pfp";
             const bool few_docs = doc_len_.size() <= 4 && !forced_pfp;
             kind = (env && std::string(env) == "direct") || reserved || few_docs ? 1 : 2;

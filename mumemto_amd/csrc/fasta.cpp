@@ -2,6 +2,7 @@
 
 #include <zlib.h>
 #include "out_file.hpp"
+#include "switches.hpp"
 
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -217,7 +218,7 @@ static size_t copy_sequence_lines_avx2(const char* q0, const char* e, uint8_t* w
     written = (size_t)(w - w0);
     return (size_t)(q - q0);
 }
-static bool have_avx2() { static const bool yes = __builtin_cpu_supports("avx2") && !std::getenv("MUMEMTO_NO_AVX2"); return yes; }
+static bool have_avx2() { static const bool yes = __builtin_cpu_supports("avx2") && !sw::on(sw::MUMEMTO_NO_AVX2); return yes; }
 #else
 static size_t copy_sequence_lines_avx2(const char*, const char*, uint8_t*, size_t, bool&, size_t, size_t& written) { written = 0; return 0; }
 static bool have_avx2() { return false; }
@@ -326,7 +327,7 @@ FastaDoc read_fasta(const std::string& path, std::vector<uint8_t>& bases) {
 FastaDoc read_fasta_replace(const std::string& path, std::vector<uint8_t>& bases) {
     size_t size = 0;
     const bool gz = file_info(path, size);
-    if (!gz && size && !std::getenv("MUMEMTO_STREAM_READER")) {
+    if (!gz && size && !sw::on(sw::MUMEMTO_STREAM_READER)) {
         bases.resize(size + 64);                    // (a plain file holds at most its size in bases)
         FastaDoc doc;
         RawSink raw{bases.data(), 0, bases.size()};
@@ -352,7 +353,7 @@ uint8_t* HostArena::ensure(size_t bytes) {
 // 256-thread host is throttled for the rest of every 100 ms period once 94 reader threads have spent it in 17 ms -- and
 // with them the thread that feeds the GPU), else what the machine has.  MUMEMTO_READ_THREADS overrides.
 size_t reader_threads() {
-    if (const char* e = std::getenv("MUMEMTO_READ_THREADS")) return (size_t)std::max(1, std::atoi(e));
+    if (sw::is_set(sw::MUMEMTO_READ_THREADS)) return (size_t)std::max(1, sw::num(sw::MUMEMTO_READ_THREADS, 0));
     size_t n = std::max(1u, std::thread::hardware_concurrency());
     if (FILE* f = std::fopen("/sys/fs/cgroup/cpu.max", "r")) {
         char quota[64] = {0};
@@ -398,7 +399,7 @@ long read_fasta_collection(const std::vector<std::string>& inputs, std::vector<F
                     if (aborted.load()) continue;
                     ChunkTarget target = hooks->chunks(i);
                     ChunkSink sink{target, slot[i + 1] - slot[i]};
-                    if (std::getenv("MUMEMTO_STREAM_READER") || !read_plain_fasta_blocks(inputs[i], sink, docs[i])) {
+                    if (sw::on(sw::MUMEMTO_STREAM_READER) || !read_plain_fasta_blocks(inputs[i], sink, docs[i])) {
                         sink.restart();                  // ('@' records, '+' lines: once more through the stream reader)
                         docs[i] = read_fasta_with<LineReader>(inputs[i], sink);
                     }
@@ -410,7 +411,7 @@ long read_fasta_collection(const std::vector<std::string>& inputs, std::vector<F
                     out.ptr[i] = out.owned[i].data(); out.len[i] = out.owned[i].size();
                 } else {
                     RawSink raw{base + slot[i], 0, slot[i + 1] - slot[i]};
-                    if (!std::getenv("MUMEMTO_STREAM_READER") && read_plain_fasta_blocks(inputs[i], raw, docs[i])) {
+                    if (!sw::on(sw::MUMEMTO_STREAM_READER) && read_plain_fasta_blocks(inputs[i], raw, docs[i])) {
                         out.ptr[i] = base + slot[i]; out.len[i] = raw.n;
                     } else {
                         RawSink sink{base + slot[i], 0, slot[i + 1] - slot[i]};

@@ -33,14 +33,6 @@ static uint32_t read_u32(const uint32_t* d, hipStream_t s) {
     return v;
 }
 
-// MMT_MEM_TRACE=1: live / peak bytes of the device heap at the stage boundaries (stderr)
-static void mem_mark(int device, const char* what) {
-    static const bool on = std::getenv("MMT_MEM_TRACE") != nullptr;
-    if (!on) return;
-    const pool::Stats s = pool::stats(device);
-    std::fprintf(stderr, "[mem] %-28s live %7.2f GB  peak %7.2f GB  mapped %7.2f GB\n", what, s.live / 1e9, s.peak / 1e9, s.mapped / 1e9);
-}
-
 namespace {
 
 // scratch of one batch (capacity elements)
@@ -82,9 +74,9 @@ RoundStats sort_batch(Batch& X, uint32_t B, const gk::Ctx& ctx, DevBuf<uint8_t>&
     prims::inclusive_max_u32(temp, X.ghead.get(), X.ghead.get(), m, st);
     uint64_t offset = (uint64_t)ctx.chars;
     const uint32_t target = 1024, limit = gk::SORT_CAP - target;
-    if (!std::getenv("MMT_GUIDED_NO_SMALL")) {                      // (the variable sends every group through the rounds: tests)
+    if (!sw::on(sw::MMT_GUIDED_NO_SMALL)) {                      // (the variable sends every group through the rounds: tests)
         gk::resolve_small(ctx, X.pos_a.get(), X.ghead.get(), X.slot_a.get(), m, offset, X.pos_b.get(), X.flags.get(), err, st,
-                          std::getenv("MMT_GUIDED_NO_SMALL_LCP") ? nullptr : lcp_out);
+                          sw::on(sw::MMT_GUIDED_NO_SMALL_LCP) ? nullptr : lcp_out);
         prims::select_indices(temp, X.flags.get(), X.idx.get(), X.count.get(), m, st);
         const uint32_t m2 = read_u32(X.count.get(), st);
         if (m2 && m2 < m) {
@@ -96,7 +88,7 @@ RoundStats sort_batch(Batch& X, uint32_t B, const gk::Ctx& ctx, DevBuf<uint8_t>&
         rs.small = m - m2;
         m = m2;
         // ... and the groups of up to 128 elements (the copies of a position in 9 .. 128 haplotypes), one wave per group
-        if (m && !std::getenv("MMT_GUIDED_NO_MEDIUM")) {
+        if (m && !sw::on(sw::MMT_GUIDED_NO_MEDIUM)) {
             // lists of (first element, size) pairs, one per size class, in key_b (dead since the first sort): m / 9 pairs at most
             const uint32_t lcap = m / 9 + 64;
             gk::medium_groups(X.ghead.get(), m, X.key_b.get(), lcap, X.count.get() + 4, st);
@@ -121,8 +113,8 @@ RoundStats sort_batch(Batch& X, uint32_t B, const gk::Ctx& ctx, DevBuf<uint8_t>&
             }
         }
     }
-    const bool no_early_giant = std::getenv("MMT_GUIDED_NO_EARLY_GIANT") != nullptr;
-    const bool no_tail = std::getenv("MMT_GUIDED_NO_TAIL") != nullptr;
+    const bool no_early_giant = sw::on(sw::MMT_GUIDED_NO_EARLY_GIANT);
+    const bool no_tail = sw::on(sw::MMT_GUIDED_NO_TAIL);
     bool tail_done = false;
     while (m) {
         if (++rs.rounds > (1 << 22)) throw std::runtime_error("parse-guided suffix sort did not converge");
@@ -170,7 +162,7 @@ RoundStats sort_batch(Batch& X, uint32_t B, const gk::Ctx& ctx, DevBuf<uint8_t>&
             prims::segmented_sort_pairs_u64_u64vals_ranges(temp, X.key_a.get(), X.key_b.get(), X.pos_a.get(), X.pos_c.get(), m,
                                                            segs, X.seg.get(), X.seg.get() + cap, 64, st);
         }
-        gk::round_heads(ctx, X.key_b.get(), X.ghead.get(), m, X.hv.get(), err, st, std::getenv("MMT_GUIDED_NO_ROUND_LCP") ? nullptr : lcp_out,
+        gk::round_heads(ctx, X.key_b.get(), X.ghead.get(), m, X.hv.get(), err, st, sw::on(sw::MMT_GUIDED_NO_ROUND_LCP) ? nullptr : lcp_out,
                         X.slot_a.get(), offset, early_giant ? X.flags.get() : nullptr);
         prims::inclusive_max_u32(temp, X.hv.get(), X.hv.get(), m, st);
         gk::round_apply(X.pos_c.get(), X.hv.get(), X.slot_a.get(), m, X.pos_b.get(), X.flags.get(), st);
@@ -192,7 +184,7 @@ RoundStats sort_batch(Batch& X, uint32_t B, const gk::Ctx& ctx, DevBuf<uint8_t>&
         if (m && m <= 32768 && !tail_done && offset < (1ull << 40) && !no_tail) {
             tail_done = true;
             gk::resolve_small(ctx, X.pos_a.get(), X.ghead.get(), X.slot_a.get(), m, offset, X.pos_b.get(), X.flags.get(), err, st,
-                              std::getenv("MMT_GUIDED_NO_SMALL_LCP") ? nullptr : lcp_out, 1024);
+                              sw::on(sw::MMT_GUIDED_NO_SMALL_LCP) ? nullptr : lcp_out, 1024);
             prims::select_indices(temp, X.flags.get(), X.idx.get(), X.count.get(), m, st);
             const uint32_t m3 = read_u32(X.count.get(), st);
             if (m3 && m3 < m) {
@@ -211,6 +203,20 @@ RoundStats sort_batch(Batch& X, uint32_t B, const gk::Ctx& ctx, DevBuf<uint8_t>&
 // buckets [blo, bhi) of gk::RunSlice; `first`: the bin's first slice).  Of its `count` suffixes `reps` are collected and sorted:
 // all of them in the plain loop, the representatives in the expansion loop.
 struct Piece { uint32_t bin, blo, bhi; uint64_t count, reps; bool slice, first; };
+
+// What MMT_GUIDED_BATCH / MMT_GUIDED_STAGE (tests) make of a stream loop's capacities; `share` and `largest` count what the loop
+// batches: text suffixes in the plain loop, representatives in the expansion loop.
+struct BatchSwitches {
+    const bool forced = sw::is_set(sw::MMT_GUIDED_BATCH);
+    uint64_t cap() const { return std::max<uint64_t>(1024, sw::num(sw::MMT_GUIDED_BATCH, 0)); }
+    // the staging list: MMT_GUIDED_STAGE decides; else under MMT_GUIDED_BATCH every run of several batches has one
+    bool staged(bool automatic, uint64_t share, uint64_t cap) const {
+        if (sw::is_set(sw::MMT_GUIDED_STAGE)) return sw::on(sw::MMT_GUIDED_STAGE);
+        return forced ? share > 2 * cap : automatic;
+    }
+    // (under MMT_GUIDED_BATCH: a few batches per pass)
+    uint64_t stage_cap(uint64_t share, uint64_t cap, uint64_t largest) const { return std::min<uint64_t>(share, std::max<uint64_t>(4 * cap, largest)); }
+};
 
 // the symbol a bin's prefix repeats (0: the bin is not a run bin)
 uint32_t run_symbol(const gk::Ctx& ctx, int prefix_chars, uint32_t b) {
@@ -348,7 +354,7 @@ void Engine::guided_prepare() {
     const bool W = wide_;
     hipStream_t st = stream_;
     const uint32_t w = S.w, m = S.n_phrases, D = S.n_distinct;
-    const bool stats = std::getenv("MMT_GUIDED_STATS") != nullptr;
+    const bool stats = sw::on(sw::MMT_GUIDED_STATS);
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto ms_since = [&](std::chrono::steady_clock::time_point t) {
         MMT_HIP(hipStreamSynchronize(st));
@@ -380,7 +386,7 @@ void Engine::guided_prepare() {
     // (a bin must fit one batch of at most 2^30 suffixes: beyond 2^38 characters -- four leading bases hold n / 256 of the
     // suffixes of a DNA text -- the bins take one character more; MMT_GUIDED_PREFIX: tests)
     if (n >= (1ull << 38)) prefix_chars = std::max(prefix_chars, std::min(15 / ctx.bits, ctx.chars));
-    if (const char* e = std::getenv("MMT_GUIDED_PREFIX")) prefix_chars = std::max(1, std::min(std::atoi(e), std::min(18 / ctx.bits, ctx.chars)));
+    if (sw::is_set(sw::MMT_GUIDED_PREFIX)) prefix_chars = std::max(1, std::min(sw::num(sw::MMT_GUIDED_PREFIX, 0), std::min(18 / ctx.bits, ctx.chars)));
     prefix_chars = std::max(1, std::min<int>(prefix_chars, (int)std::min<uint32_t>(stream_min_len_, 64u)));
     // (expansion: every occurrence of a phrase suffix must lie in the bin of its representative -- a phrase suffix has at
     // least w characters, so a bin's prefix must not be longer than that)
@@ -392,7 +398,7 @@ void Engine::guided_prepare() {
     ctx.T = text_ref(); ctx.n = n; ctx.w = w; ctx.code = d_code_.get(); ctx.m = m;
     for (int k = 0; k < 4; k++) ctx.acgt[k] = code[(uint8_t)"ACGT"[k]];
     ctx.acgt_lut = (uint32_t)ctx.acgt[0] | ((uint32_t)ctx.acgt[1] << 8) | ((uint32_t)ctx.acgt[2] << 16) | ((uint32_t)ctx.acgt[3] << 24);
-    ctx.dense_ok = ctx.acgt[0] && ctx.acgt[1] && ctx.acgt[2] && ctx.acgt[3] && ctx.chars <= 32 && !std::getenv("MMT_GUIDED_NO_DENSE");
+    ctx.dense_ok = ctx.acgt[0] && ctx.acgt[1] && ctx.acgt[2] && ctx.acgt[3] && ctx.chars <= 32 && !sw::on(sw::MMT_GUIDED_NO_DENSE);
 
     // ---- phrase ends: rank directory and successor table over the cut bits ----
     const uint64_t n_words = S.tmask.size() * sizeof(uint16_t) / 8 / 64 * 64;     // whole blocks of 4096 positions
@@ -405,7 +411,7 @@ void Engine::guided_prepare() {
     // (... and only then: a rank query on the bits is two independent lines -- directory word + the 512 positions' words --,
     // on the list a search of two or three dependent round trips; a rank's share of configs[3], 79 G characters packed to
     // 20 GB, keeps its 10 GB of bits)
-    const bool cut_list = std::getenv("MMT_CUT_LIST") ? std::atoi(std::getenv("MMT_CUT_LIST")) != 0 : (packed_ && n >= (1ull << 37));
+    const bool cut_list = sw::is_set(sw::MMT_CUT_LIST) ? sw::on(sw::MMT_CUT_LIST) : (packed_ && n >= (1ull << 37));
     if (cut_list) {
         DevBuf<uint32_t> bcount;
         bcount.ensure(n_blocks + 2); S.g_brank.ensure(n_blocks + 2);
@@ -510,7 +516,7 @@ void Engine::guided_prepare() {
         // (pfp.cpp::pfp_prepare_emitter): occurrences ordered by (phrase, rank of the following parse suffix)
         const int shift = bit_width_u64((uint64_t)m + 1);
         const uint32_t pos_bits = W ? (uint32_t)bit_width_u64(n + w + 1) : 32u;
-        const bool rec12 = (uint32_t)shift + pos_bits > 64 || std::getenv("MMT_OCC_REC12") != nullptr;
+        const bool rec12 = (uint32_t)shift + pos_bits > 64 || sw::on(sw::MMT_OCC_REC12);
         S.occ_start.ensure((size_t)D + 2);
         S.occ_ids.ensure((size_t)m + 1); S.occ_ts.ensure((size_t)m + 1);
         {
@@ -544,7 +550,7 @@ void Engine::guided_prepare() {
     // the same alpha -- gk::med_before asks the ids before it compares characters)
     S.sa_p.release(); S.parse.release(); S.rep.release(); S.prank.release(); S.pstart.release();
     S.plen.release(); S.dlen.release(); S.dstart.release();
-    ctx.pid = std::getenv("MMT_GUIDED_NO_PID") && !S.expand ? nullptr : S.pid.get();
+    ctx.pid = sw::on(sw::MMT_GUIDED_NO_PID) && !S.expand ? nullptr : S.pid.get();
     e5.stop(st);
     if (stats) std::fprintf(stderr, "[guided] parse of %u phrases sorted in %.1f ms (%d rounds)\n", m, ms_since(t0), S.rounds_parse);
     ctx.skip = 0; ctx.isa_p = S.isa_p.get();
@@ -554,7 +560,7 @@ void Engine::guided_prepare() {
         // the parse rank rides in the record when it fits next to the position (MMT_GUIDED_NO_RANK: never -- tests)
         // (representatives never ask for a parse rank: their records carry the length of alpha)
         const uint32_t pb = (uint32_t)bit_width_u64(n + w + 1);
-        if (pb + (uint32_t)bit_width_u64(m) <= 64 && !std::getenv("MMT_GUIDED_NO_RANK")) { ctx.pos_bits = pb; ctx.rec_rank = 1; }
+        if (pb + (uint32_t)bit_width_u64(m) <= 64 && !sw::on(sw::MMT_GUIDED_NO_RANK)) { ctx.pos_bits = pb; ctx.rec_rank = 1; }
     }
     S.ms[2] = 0; S.ms[3] = e3.ms(); S.ms[4] = 0; S.ms[5] = e5.ms();
     S.bwt_ready = true;
@@ -579,8 +585,8 @@ void Engine::build_giant(const std::vector<uint64_t>& hist) {
     ctx.g_n = 0;
     ctx.g_depth = std::max<uint32_t>(24u, (12u * S.p + (uint32_t)ctx.chars - 1) / (uint32_t)ctx.chars) * (uint32_t)ctx.chars;
     S.gi_occ = S.gi_distinct = S.gi_chars = 0;
-    if (std::getenv("MMT_GUIDED_NO_GIANT")) return;
-    if (const char* c = std::getenv("MMT_GIANT_DEPTH")) ctx.g_depth = (uint32_t)std::max(1, std::atoi(c)) * (uint32_t)ctx.chars;
+    if (sw::on(sw::MMT_GUIDED_NO_GIANT)) return;
+    if (sw::is_set(sw::MMT_GIANT_DEPTH)) ctx.g_depth = (uint32_t)std::max(1, sw::num(sw::MMT_GIANT_DEPTH, 0)) * (uint32_t)ctx.chars;
     DevBuf<uint32_t> flags, gids, count;
     count.ensure(4);
     // distinct phrases longer than g_depth (dlen counts the terminator) ...
@@ -595,7 +601,7 @@ void Engine::build_giant(const std::vector<uint64_t>& hist) {
     // phrase longer than g_depth: the short phrases between and beside giant ones are the ones that sit in those groups.
     // (MMT_GIANT_PROMOTE=<steps>, 0: none)
     DevBuf<uint32_t> occ_flag;                  // per phrase of the parse: lies in a phrase of the giant dictionary
-    const int promote = std::getenv("MMT_GIANT_PROMOTE") ? std::max(0, std::atoi(std::getenv("MMT_GIANT_PROMOTE"))) : 4;
+    const int promote = std::max(0, sw::num(sw::MMT_GIANT_PROMOTE, 4));
     bool promoted = false;
     uint32_t nG = 0;
     uint64_t nd64 = 0;
@@ -635,7 +641,7 @@ void Engine::build_giant(const std::vector<uint64_t>& hist) {
         MMT_HIP(hipMemcpyAsync(&nd64, total.get(), 8, hipMemcpyDeviceToHost, st));
         MMT_HIP(hipStreamSynchronize(st));
         nd64 += 1;
-        if (std::getenv("MMT_GUIDED_STATS"))
+        if (sw::on(sw::MMT_GUIDED_STATS))
             std::fprintf(stderr, "[guided] giant dictionary with the phrases within %d steps of a giant occurrence: %u phrases, %llu characters\n",
                          steps, nG, (unsigned long long)nd64);
         if (nd64 < 0xffffff00ull || a + 1 == attempts.size()) break;
@@ -735,7 +741,7 @@ void Engine::build_giant(const std::vector<uint64_t>& hist) {
     ctx.g_k = S.gi_k.get(); ctx.g_ps = S.gi_ps.get(); ctx.g_base = S.gi_base.get(); ctx.g_n = nO;
     ctx.g_isa = S.gi_isa.get(); ctx.g_grp = S.gi_grp.get(); ctx.g_bits = S.gi_bits.get(); ctx.g_rank = S.gi_rank.get();
     ctx.g_rmq.sl = S.gi_lcp.get(); ctx.g_rmq.bmin = S.gi_bmin.get(); ctx.g_rmq.m = nd; ctx.g_rmq.nb = S.gi_nb;
-    if (std::getenv("MMT_GUIDED_STATS"))
+    if (sw::on(sw::MMT_GUIDED_STATS))
         std::fprintf(stderr, "[guided] %u giant distinct phrases (%u characters, sorted in %d rounds), %u occurrences in the parse\n",
                      nG, nd, rounds, nO);
 }
@@ -800,7 +806,7 @@ void Engine::guided_stream(ScanState& SS, const mmt_params& p) {
     const uint64_t n = n_;
     hipStream_t st = stream_;
     DevBuf<unsigned long long> prof;
-    if (std::getenv("MMT_GUIDED_PROF")) {
+    if (sw::on(sw::MMT_GUIDED_PROF)) {
         prof.ensure(16);
         MMT_HIP(hipMemsetAsync(prof.get(), 0, 16 * 8, st));
         S.gctx.prof = prof.get();
@@ -822,7 +828,7 @@ void Engine::guided_stream(ScanState& SS, const mmt_params& p) {
     const gk::Ctx& ctx = S.gctx;
     const int prefix_chars = S.g_prefix;
     const std::vector<uint64_t>& bins = S.g_bins;
-    const bool stats = std::getenv("MMT_GUIDED_STATS") != nullptr;
+    const bool stats = sw::on(sw::MMT_GUIDED_STATS);
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto t0 = now();
     const GuidedShare sh = guided_share(p);
@@ -845,7 +851,8 @@ void Engine::guided_stream(ScanState& SS, const mmt_params& p) {
                          8.0 * (double)((n + gk::TILE - 1) / gk::TILE) - 6.0 * 1073741824.0;
     const uint64_t fit = avail > 0 ? (uint64_t)(avail / per_element) : 0;
     cap64 = std::min(cap64, std::max<uint64_t>(fit, 1u << 20));
-    if (const char* c = std::getenv("MMT_GUIDED_BATCH")) cap64 = std::max<uint64_t>(1024, std::strtoull(c, nullptr, 10));
+    const BatchSwitches bsw;
+    if (bsw.forced) cap64 = bsw.cap();
     if (largest > cap64) {
         if (largest > fit || largest >= 0xfffffff0ull)
             throw std::runtime_error("guided sort: " + std::to_string(largest) + " suffixes share their first " +
@@ -860,12 +867,10 @@ void Engine::guided_stream(ScanState& SS, const mmt_params& p) {
     // a share of configs[3], 79 G x 86, ran 38 - 45 s without the list and 42 - 48 s with it: smaller batches, keys looked up at
     // random instead of rolled along the tile).
     const uint64_t share = pre[bin_hi] - pre[bin_lo];
-    bool staged = share > 2 * cap64 && (double)n * ((double)share / (double)cap64) >= 2e13;
-    if (const char* c = std::getenv("MMT_GUIDED_STAGE")) staged = std::atoi(c) != 0;
-    else if (std::getenv("MMT_GUIDED_BATCH")) staged = share > 2 * cap64;            // (tests: every run of several batches)
+    bool staged = bsw.staged(share > 2 * cap64 && (double)n * ((double)share / (double)cap64) >= 2e13, share, cap64);
     uint64_t stage_cap = 0;
     if (staged) {
-        if (std::getenv("MMT_GUIDED_BATCH")) stage_cap = std::min<uint64_t>(share, std::max<uint64_t>(4 * cap64, largest));   // (tests: a few batches per pass)
+        if (bsw.forced) stage_cap = bsw.stage_cap(share, cap64, largest);
         else {
             // (what a full batch leaves, if that holds two batches' worth; else 40 % of what the batches may use)
             const double spare = avail - (double)cap64 * per_element;
@@ -968,7 +973,7 @@ void Engine::guided_stream_expand(ScanState& SS, const mmt_params& p) {
     const uint32_t n_bins = S.g_nbins;
     const std::vector<uint64_t>& bins = S.g_bins;
     const std::vector<uint64_t>& rbins = S.g_bins_rep;
-    const bool stats = std::getenv("MMT_GUIDED_STATS") != nullptr;
+    const bool stats = sw::on(sw::MMT_GUIDED_STATS);
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto t0 = now();
     if (!S.ptab.get() || (!S.occ.get() && !S.occ12.get())) throw std::runtime_error("expansion: the inverted lists are gone");
@@ -988,7 +993,7 @@ void Engine::guided_stream_expand(ScanState& SS, const mmt_params& p) {
     // whole genomes with 60 Mbp of gaps each -- is not cut by more leading characters, but its order is known in closed form
     // (guided_kernels.hip RunSlice): when it exceeds a batch or a window it is produced in slices.  Only in the capped modes: an
     // interval of an uncapped mode may be as long as its bin, and a window must hold it.  (MMT_GUIDED_SLICE=<suffixes>: tests)
-    const uint64_t slice_env = std::getenv("MMT_GUIDED_SLICE") ? std::strtoull(std::getenv("MMT_GUIDED_SLICE"), nullptr, 10) : 0;
+    const uint64_t slice_env = sw::num(sw::MMT_GUIDED_SLICE, 0);
     // (the closed form needs every phrase suffix that begins inside a run to reach beyond the run's end -- all occurrences of a
     // representative then share (r, X0).  That holds unless the window of w equal symbols is itself a trigger of the parse
     // (newscan.hpp:106-114,321: hash of c^w divisible by p -- a phrase would end at EVERY position of the run); the automatic
@@ -1001,7 +1006,7 @@ void Engine::guided_stream_expand(ScanState& SS, const mmt_params& p) {
     std::vector<char> keep_whole(n_bins, 0);        // run bins whose slices would not fit a batch either: produced as whole bins
     auto sliceable = [&](uint32_t b) {
         const uint32_t sym = run_symbol(ctx, prefix_chars, b);
-        return capped && sym != 0 && !keep_whole[b] && !run_triggers(sym) && !std::getenv("MMT_GUIDED_NO_SLICES");
+        return capped && sym != 0 && !keep_whole[b] && !run_triggers(sym) && !sw::on(sw::MMT_GUIDED_NO_SLICES);
     };
     uint64_t largest = 0, largest_rep = 0, share = 0, share_rep = 0, largest_any = 0;
     for (uint32_t b = bin_lo; b < bin_hi; b++) { largest_any = std::max(largest_any, bins[b]); share += bins[b]; share_rep += rbins[b]; }
@@ -1018,7 +1023,7 @@ void Engine::guided_stream_expand(ScanState& SS, const mmt_params& p) {
     // its first batch, and at 0.76 its batches were 312 M representatives -- 64 passes over the text -- where 0.86 gave 723 M, 29
     // passes and 7 s less; 0.82 keeps the peak of such a share near 255 GB of the 288)
     double heap_frac = sink_writer_.active() && sink_discard_ ? 0.90 : 0.82;
-    if (const char* c = std::getenv("MMT_EXPAND_HEAP_FRAC")) heap_frac = std::min(0.95, std::max(0.3, std::atof(c)));
+    if (const char* c = sw::text(sw::MMT_EXPAND_HEAP_FRAC)) heap_frac = std::min(0.95, std::max(0.3, std::atof(c)));
     const double avail = std::min(0.80 * free_now, heap_frac * (free_now + live_now) - live_now) - 2.0 * per_out * (double)head_room -
                          8.0 * (double)((n + gk::TILE - 1) / gk::TILE) - 4.0 * 1073741824.0;
     const uint64_t WIN_MAX = 1ull << 31;                                           // (a window and its tail stay well below 2^32 entries)
@@ -1028,6 +1033,7 @@ void Engine::guided_stream_expand(ScanState& SS, const mmt_params& p) {
     DevBuf<uint64_t> run_lead;
     DevBuf<uint8_t> run_first, run_follow;
     gk::RunSlice run_tab;                    // the tables of the tiles (sym, blo, bhi are set per batch)
+    const BatchSwitches bsw;
     uint32_t sliced_bins = 0;
     const uint32_t n_tiles = (uint32_t)((n + gk::TILE - 1) / gk::TILE);
     for (int attempt = 0;; attempt++) {
@@ -1040,8 +1046,8 @@ void Engine::guided_stream_expand(ScanState& SS, const mmt_params& p) {
     rep_cap = avail > 0 ? (uint64_t)((avail - (double)win_cap * per_out) / per_rep) : 0;
     rep_cap = std::min<uint64_t>(std::max<uint64_t>(rep_cap, 1u << 20), 1ull << 30);
     rep_cap = std::min<uint64_t>(rep_cap, std::max<uint64_t>(share_rep, 1024));
-    if (const char* c = std::getenv("MMT_GUIDED_BATCH")) {                         // (tests: small batches, two or three windows each)
-        rep_cap = std::max<uint64_t>(1024, std::strtoull(c, nullptr, 10));
+    if (bsw.forced) {                                                           // (tests: small batches, two or three windows each)
+        rep_cap = bsw.cap();
         const double ratio = (double)std::max<uint64_t>(share, 1) / (double)std::max<uint64_t>(share_rep, 1);
         win_cap = std::max<uint64_t>(1024, (uint64_t)(0.4 * (double)rep_cap * ratio));
     }
@@ -1050,12 +1056,11 @@ void Engine::guided_stream_expand(ScanState& SS, const mmt_params& p) {
     // Part of the memory becomes a list of the representatives of the next batches' bins (8 bytes each), filled by one pass.
     // (1e12 since the entries are four bytes, 2e13 before: a rank's share of configs[3] -- 79 G characters, 15 - 30 batches -- gains a
     // second of its 14, and three of 29 with realistic content: 4 and 14 passes over the text instead of 15 and 36)
-    staged = share_rep > 2 * rep_cap && (double)n * ((double)share_rep / (double)std::max<uint64_t>(rep_cap, 1)) >= 1e12;
-    if (const char* c = std::getenv("MMT_GUIDED_STAGE")) staged = std::atoi(c) != 0;
-    else if (std::getenv("MMT_GUIDED_BATCH")) staged = share_rep > 2 * rep_cap;      // (tests: every run of several batches)
+    staged = bsw.staged(share_rep > 2 * rep_cap && (double)n * ((double)share_rep / (double)std::max<uint64_t>(rep_cap, 1)) >= 1e12,
+                           share_rep, rep_cap);
     stage_cap = 0;
     if (staged) {
-        if (std::getenv("MMT_GUIDED_BATCH")) stage_cap = std::min<uint64_t>(share_rep, std::max<uint64_t>(4 * rep_cap, largest_rep));
+        if (bsw.forced) stage_cap = bsw.stage_cap(share_rep, rep_cap, largest_rep);
         else {
             const double for_reps = std::max(avail - (double)win_cap * per_out, 0.0);
             const double stage_bytes = 0.4 * for_reps;

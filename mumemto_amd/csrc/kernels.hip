@@ -973,12 +973,7 @@ void round_fused(const uint32_t* sac, const uint32_t* headc, const uint32_t* pos
 // elements of one LDS tile of k_round_fused (MMT_ROUND_CAP = 1024 / 2048: tuning aid; a power of two -- the bitonic path
 // of a tile pads to the next power of two of its length and the LDS columns hold CAP entries)
 uint32_t round_fused_cap() {
-    static const uint32_t cap = [] {
-        const char* e = std::getenv("MMT_ROUND_CAP");
-        const int v = e ? std::atoi(e) : 2048;
-        return (uint32_t)(v == 1024 ? v : 2048);
-    }();
-    return cap;
+    return sw::num(sw::MMT_ROUND_CAP, 2048) == 1024 ? 1024u : 2048u;
 }
 void round_big_keys(const uint8_t* tile_big, const uint32_t* bound, uint32_t target, uint32_t n_tiles, const uint32_t* sac,
                     const uint32_t* headc, const uint32_t* rank, uint32_t n, uint32_t h, int shift, uint64_t* keys,
@@ -2138,7 +2133,7 @@ __global__ __launch_bounds__(BLOCK) void k_scan_wide(ScanArgs a, uint32_t w, int
 }
 
 static uint32_t wide_threshold() {
-    static const uint32_t t = getenv("MMT_SCAN_WIDE_AT") ? (uint32_t)atoi(getenv("MMT_SCAN_WIDE_AT")) : 1000u;
+    const uint32_t t = (uint32_t)sw::num(sw::MMT_SCAN_WIDE_AT, 1000);
     return t;
 }
 bool scan_needs_wide_docs(size_t n_docs) { return n_docs > (size_t)wide_threshold() + 1; }
@@ -2170,9 +2165,9 @@ static void launch_scan(const ScanArgs& a, hipStream_t s, unsigned blocks_per_cu
     if (halo > 4 * B) halo = 4 * B;                        // beyond this the walk reads the cached global columns
     if (halo < w + 1) exact = false;
     // the 94-document shape (64 <= w < 128, exact windows): block-wise window minima instead of level-wise tables
-    static const bool no_vh = std::getenv("MMT_SCAN_NO_VH") != nullptr;
+    const bool no_vh = sw::on(sw::MMT_SCAN_NO_VH);
     // (... and the general modes with such a window -- 94 documents, -k -1: the configs[4] instantiation -- take the same tables)
-    static const bool two_pass = std::getenv("MMT_SCAN_TWO_PASS") != nullptr;     // tests: the general modes' two-pass form
+    const bool two_pass = sw::on(sw::MMT_SCAN_TWO_PASS);     // tests: the general modes' two-pass form
     const bool onepass = !exact && !a.emit_all && !two_pass;
     const bool vh = (exact || onepass) && klev == 6 && halo >= w + 1 && !no_vh && VH_OUT > 0;
     const size_t out_cap = vh ? (size_t)VH_OUT : (size_t)OUT_CAP;
@@ -2239,12 +2234,8 @@ void scan_intervals(const ScanArgs& a, hipStream_t s) {
     // measured on MI355X (tests/scan_sweep.sh, profiles/): workgroups of 256 threads x 8 positions (39.7 KB of LDS
     // with both column buffers: four resident workgroups per CU) and a grid of 16 per CU are best for 16 and for
     // 94 documents alike; 512 x 8 is 5 % slower, 512 x 12 leaves one workgroup per CU.
-    static int variant = -1, bpc = 16;
-    if (variant < 0) {
-        const char* v = getenv("MMT_SCAN_VARIANT"); variant = v ? atoi(v) : 0;
-        const char* g = getenv("MMT_SCAN_BPC"); if (g) bpc = atoi(g);
-    }
-    switch (variant) {
+    const int bpc = sw::num(sw::MMT_SCAN_BPC, 16);
+    switch (sw::num(sw::MMT_SCAN_VARIANT, 0)) {
         case 1: launch_scan<512, 1, 256>(a, s, bpc); break;
         case 2: launch_scan<512, 2, 256>(a, s, bpc); break;
         default: launch_scan<256, 2, 256, 128>(a, s, bpc); break;
@@ -2434,7 +2425,7 @@ static void verify_typed(const VerifyArgs& v, hipStream_t s) {
     // MUM mode, <= 64 documents (then an accepted interval has <= 64 entries)
     bool fast = a.max_doc_freq == 1 && a.n_docs <= 64;
     uint64_t waves_needed = a.n_cand;
-    static const bool packed_off = getenv("MMT_VERIFY_UNPACKED") != nullptr;      // tests: the wave-per-candidate kernel
+    const bool packed_off = sw::on(sw::MMT_VERIFY_UNPACKED);      // tests: the wave-per-candidate kernel
     if (fast && a.n_docs <= 32 && !packed_off) {
         constexpr int W = 4;
         const int sub = a.n_docs <= 8 ? 8 : (a.n_docs <= 16 ? 16 : 32);

@@ -109,7 +109,7 @@ void merge_release_scratch() {
 }
 
 MergedRows anchor_merge(Engine& e, const mmt_partition* parts, size_t k, uint32_t min_len) {
-    const bool dbg = std::getenv("MMT_MERGE_DEBUG") != nullptr;
+    const bool dbg = sw::on(sw::MMT_MERGE_DEBUG);
     hipStream_t st = e.stream();
     MMT_HIP(hipSetDevice(e.device()));
     auto T0 = std::chrono::steady_clock::now();
@@ -404,7 +404,7 @@ MergedRows anchor_merge_by_ranges(Engine& e, const mmt_partition* parts, size_t 
         dev[g].rows_on_device = 1;
     }
     MMT_HIP(hipStreamSynchronize(st));
-    const bool dbg = std::getenv("MMT_MERGE_DEBUG") != nullptr;
+    const bool dbg = sw::on(sw::MMT_MERGE_DEBUG);
     std::vector<MergedRows> pieces;
     for (int r = 0; r < slices; r++) {
         uint64_t lo, hi, base;
@@ -514,9 +514,9 @@ void write_merged_text(Engine& e, const MergedRows& m, const std::string& path) 
     hipStream_t st = e.stream();
     MMT_HIP(hipSetDevice(e.device()));
     size_t piece_bytes = MERGED_TEXT_PIECE;
-    if (const char* c = std::getenv("MMT_MERGED_TEXT_PIECE")) piece_bytes = std::max<size_t>(std::strtoull(c, nullptr, 10), 4096);
+    if (sw::is_set(sw::MMT_MERGED_TEXT_PIECE)) piece_bytes = std::max<size_t>(sw::num(sw::MMT_MERGED_TEXT_PIECE, 0), 4096);
     // ~ (digits + comma + strand + comma) per cell: an upper bound good enough to choose the route
-    const bool one_piece = !std::getenv("MMT_MERGED_TEXT_PIECE") && (double)n * (double)m.n_docs * 24.0 < (double)MERGED_TEXT_ONE_PIECE;
+    const bool one_piece = !sw::is_set(sw::MMT_MERGED_TEXT_PIECE) && (double)n * (double)m.n_docs * 24.0 < (double)MERGED_TEXT_ONE_PIECE;
     if (!n || one_piece) {
         size_t bytes = 0;
         const char* host = stage_merged_text(e, m, &bytes);

@@ -78,7 +78,7 @@ int main(int argc, char** argv) {
             mp[i].strands = parts[i].strands.data(); mp[i].thresh = parts[i].thresh.data();
             mp[i].thresh_len = parts[i].thresh.size(); mp[i].thresh_on_device = 0; mp[i].rows_on_device = 0;
         }
-        mmt::Engine eng(std::getenv("MUMEMTO_DEVICE") ? std::atoi(std::getenv("MUMEMTO_DEVICE")) : 0, nullptr);
+        mmt::Engine eng(mmt::env_device(), nullptr);
         mmt::MergedRows m = mmt::anchor_merge(eng, mp.data(), mp.size(), min_len);
         mmt::download_merged(eng, m);
         bool out_bumbl = ends_with(output, ".bumbl"), out_mums = ends_with(output, ".mums");

@@ -252,7 +252,7 @@ void ParseLcp::build(const TextRef& v, uint64_t nv, const uint32_t* sa_p, const 
     MMT_HIP(hipMemcpyAsync(&bad, counts.get() + 3, 4, hipMemcpyDeviceToHost, s));
     MMT_HIP(hipStreamSynchronize(s));
     if (bad) throw std::runtime_error("parse LCP construction: " + std::to_string(bad) + " inconsistent entries");
-    if (std::getenv("MMT_LCP_STATS"))
+    if (sw::on(sw::MMT_LCP_STATS))
         std::fprintf(stderr, "[parse lcp] %u parse suffixes, %u irreducible, %u matches beyond %d characters\n", m, n_irreducible,
                      n_long, CMP_STEPS * 64);
 }

@@ -37,8 +37,7 @@ uint64_t Engine::auto_max_text() const {
     const double small = (0.95 * (double)pool::available(device_) - 1073741824.0) / 30.0;
     if (small > 0 && (uint64_t)small > max_text) max_text = std::min<uint64_t>((uint64_t)small, 1ull << 30);
     // one variable for the library and the command line (MMT_MAX_TEXT: the older name)
-    for (const char* name : {"MUMEMTO_MAX_TEXT", "MMT_MAX_TEXT"})
-        if (const char* c = std::getenv(name)) { max_text = std::strtoull(c, nullptr, 10); break; }
+    max_text = sw::num(sw::MUMEMTO_MAX_TEXT, sw::num(sw::MMT_MAX_TEXT, max_text));
     return max_text;
 }
 
@@ -99,8 +98,7 @@ void Engine::run_partitioned_docs(const uint8_t* const* doc_ptr, const uint64_t*
         try {
             // (a text that will be packed -- two bits per character -- never has its raw bases on the device as a whole:
             // they go through a staging buffer document by document; MMT_INPUT_DEFERRED=1 forces that route for tests)
-            const bool defer = std::getenv("MMT_INPUT_DEFERRED") ? std::atoi(std::getenv("MMT_INPUT_DEFERRED")) != 0
-                                                                  : want_packed_text_of(total, true);
+            const bool defer = sw::is_set(sw::MMT_INPUT_DEFERRED) ? sw::on(sw::MMT_INPUT_DEFERRED) : want_packed_text_of(total, true);
             if (defer) set_input_host_docs_deferred(doc_ptr, doc_len, n_docs);
             else set_input_host_docs(doc_ptr, doc_len, n_docs);
             run_once_dropping_input(p);
@@ -127,7 +125,7 @@ void Engine::run_partitioned_docs(const uint8_t* const* doc_ptr, const uint64_t*
     // {anchor + 12} x 3.05 Gbp on a device with 200 GB free ran out of memory twice before its partitions were small enough,
     // tests/big_reserve.py; the attempt loop below catches what this formula still gets wrong).
     // (a partition itself: its text, the tables of its parse and one batch of the producer -- auto_max_text)
-    if (auto_limit && !std::getenv("MMT_MAX_TEXT") && !std::getenv("MUMEMTO_MAX_TEXT")) {
+    if (auto_limit && !sw::is_set(sw::MMT_MAX_TEXT) && !sw::is_set(sw::MUMEMTO_MAX_TEXT)) {
         const double budget = 0.95 * (double)pool::available(device_) - 32.0 * (double)doc_len[0] - 24.0 * 1073741824.0;
         const uint64_t fit = budget > 0 ? (uint64_t)(budget / 4.0) : 0;
         max_text = std::min(max_text, std::max<uint64_t>(fit, 1));
@@ -276,7 +274,7 @@ void Engine::run_partitioned_docs(const uint8_t* const* doc_ptr, const uint64_t*
             if (!auto_limit || tries >= 4 || max_text <= smallest) throw;
             forget_last_run();                 // everything the failed attempt held goes back to the heap
             max_text = std::max<uint64_t>(smallest, (uint64_t)(0.6 * (double)max_text));
-            if (std::getenv("MUMEMTO_TIMING") || std::getenv("MMT_MEM_TRACE"))
+            if (sw::on(sw::MUMEMTO_TIMING) || sw::on(sw::MMT_MEM_TRACE))
                 std::fprintf(stderr, "[partitions] out of device memory: once more with at most %llu text characters a partition\n",
                              (unsigned long long)max_text);
         }

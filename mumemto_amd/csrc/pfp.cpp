@@ -32,14 +32,6 @@ static void offsets_from_counts(DevBuf<uint8_t>& temp, const uint32_t* counts, P
     else prims::exclusive_sum_u32(temp, counts, out.p32(), n, s);
 }
 
-// MMT_MEM_TRACE=1: live / peak bytes of the device heap at the stage boundaries (stderr)
-static void mem_mark(int device, const char* what) {
-    static const bool on = std::getenv("MMT_MEM_TRACE") != nullptr;
-    if (!on) return;
-    const pool::Stats s = pool::stats(device);
-    std::fprintf(stderr, "[mem] %-28s live %7.2f GB  peak %7.2f GB  mapped %7.2f GB\n", what, s.live / 1e9, s.peak / 1e9, s.mapped / 1e9);
-}
-
 // A2 + the dictionary half of A3: phrases, distinct phrases, dictionary text with its suffix
 // array / LCP, phrase ranks, parse.  Requires build_text() to have run.
 // keep_dict_inputs: the phrase table and V stay (PREFIX.dict is written from them: -P / parse_only).
@@ -97,7 +89,7 @@ void Engine::pfp_parse(uint32_t w, uint32_t p, bool keep_dict_inputs) {
     pk::phrase_hash(v, S.pstart.get(), S.plen.get(), m, S.h1.get(), S.pinfo.get(), W, st);
     pk::iota(S.iota.get(), m, st);
     S.dflags.ensure(m); S.scan.ensure(m);
-    for (int attempt = std::getenv("MMT_PFP_TWO_FINGERPRINTS") ? 1 : 0;; attempt++) {     // the variable forces the rare path (tests)
+    for (int attempt = sw::on(sw::MMT_PFP_TWO_FINGERPRINTS) ? 1 : 0;; attempt++) {     // the variable forces the rare path (tests)
         if (attempt == 0) {
             // order by the first fingerprint alone; equal phrases are adjacent unless two different phrases share it
             prims::sort_pairs_u64_u32(d_temp_, S.h1.get(), S.hk_b.get(), S.iota.get(), S.order.get(), m, 0, 64, st);
@@ -151,7 +143,7 @@ void Engine::pfp_parse(uint32_t w, uint32_t p, bool keep_dict_inputs) {
         // suffixes are then sorted themselves, with the parse as the tie-breaker (guided.cpp).
         S.guided = false;
         if (!keep_dict_inputs) {
-            const char* env = std::getenv("MUMEMTO_PRODUCER");
+            const char* env = sw::text(sw::MUMEMTO_PRODUCER);
             const double tables = 46.0 * (double)dict_len64, sorter = 49.0 * (double)std::max<uint64_t>(dict_len64, m);
             const double need = tables + sorter;
             S.guided = producer_ == 3 || producer_ == 4 || pfp_want_guided_ || (env && (std::string(env) == "guided" || std::string(env) == "expand")) ||
@@ -172,7 +164,7 @@ void Engine::pfp_parse(uint32_t w, uint32_t p, bool keep_dict_inputs) {
                 // producer took 104, at the same peak)
                 S.expand = producer_ == 4 || (env && std::string(env) == "expand") ||
                            (!named_plain && (double)dict_len64 < 0.5 * (double)n);
-                if (const char* x = std::getenv("MUMEMTO_EXPAND")) S.expand = std::atoi(x) != 0;
+                if (sw::is_set(sw::MUMEMTO_EXPAND)) S.expand = sw::on(sw::MUMEMTO_EXPAND);
             }
             if (S.guided) {
                 S.dict_len = 0;
@@ -193,7 +185,7 @@ void Engine::pfp_parse(uint32_t w, uint32_t p, bool keep_dict_inputs) {
     S.dict.ensure((size_t)nd + 64); S.dinfo.ensure(nd);
     MMT_HIP(hipMemsetAsync(S.dict.get() + nd, 0, 64, st));
     // room for the byte before each position in the phrase-id word (MMT_PFP_NO_PACK: the other path, for tests)
-    const bool pack_prev = D < (1u << 24) && !std::getenv("MMT_PFP_NO_PACK");
+    const bool pack_prev = D < (1u << 24) && !sw::on(sw::MMT_PFP_NO_PACK);
     pk::copy_dict(v, S.pstart.get(), S.plen.get(), S.rep.get(), S.dstart.get(), D, S.dict.get(),
                   S.dinfo.get(), nd, pack_prev, W, st);
     if (slim) S.dstart.release();
@@ -212,7 +204,7 @@ void Engine::pfp_parse(uint32_t w, uint32_t p, bool keep_dict_inputs) {
     // every 0x01 (end of a phrase) is a unique terminator, ordered by position: what follows it never matters, so
     // a suffix is final as soon as the compared prefix reaches the end of its phrase (one key bit says so)
     int chars = std::min(63 / bits, 63);
-    if (const char* e = std::getenv("MMT_DICT_KEY_CHARS")) chars = std::max(4, std::min(chars, std::atoi(e)));      // (tuning aid)
+    if (sw::is_set(sw::MMT_DICT_KEY_CHARS)) chars = std::max(4, std::min(chars, sw::num(sw::MMT_DICT_KEY_CHARS, 0)));      // (tuning aid)
     d_code_.ensure(256);
     MMT_HIP(hipMemcpyAsync(d_code_.get(), code, 256, hipMemcpyHostToDevice, st));
     S.sa_d.ensure(nd); S.rank_d.ensure(nd);
@@ -221,7 +213,7 @@ void Engine::pfp_parse(uint32_t w, uint32_t p, bool keep_dict_inputs) {
     // orders the suffixes inside them by (end of the run, what follows) instead of doubling its way through (sorter.hpp)
     const uint32_t run_cap = 1u << 20;
     DevBuf<uint32_t> run_ends, run_sorted, run_count;
-    const bool want_runs = bits <= 3 && !std::getenv("MMT_NO_RUN_REFINE");          // (MMT_NO_RUN_REFINE: plain doubling, A/B)
+    const bool want_runs = bits <= 3 && !sw::on(sw::MMT_NO_RUN_REFINE);          // (MMT_NO_RUN_REFINE: plain doubling, A/B)
     if (want_runs) {
         run_ends.ensure(run_cap); run_count.ensure(4);
         MMT_HIP(hipMemsetAsync(run_count.get(), 0, 16, st));
@@ -487,7 +479,7 @@ void Engine::pfp_emit_codes(int shift) {
     hipStream_t st = stream_;
     S.decode = pk::BwtDecode{};
     S.fb_bits = 0; S.key_shift = shift;
-    if (!std::getenv("MMT_PFP_NO_BWT_CODE")) {
+    if (!sw::on(sw::MMT_PFP_NO_BWT_CODE)) {
         std::vector<uint64_t> hist;
         d2h(hist, d_hist_.get(), 256, st);
         std::vector<uint8_t> code(256, 0);
@@ -546,7 +538,7 @@ void Engine::pfp_emit_window(uint64_t b0, uint64_t c1, int set) {
     };
     const uint64_t FB_LIMIT = 0xfffffff0ull;                              // 32-bit offsets inside one launch
     uint64_t per_launch = t_hi - t_lo;
-    if (const char* c = std::getenv("MMT_EMIT_TILES")) per_launch = std::max<uint64_t>(1, std::strtoull(c, nullptr, 10));
+    if (sw::is_set(sw::MMT_EMIT_TILES)) per_launch = std::max<uint64_t>(1, sw::num(sw::MMT_EMIT_TILES, 0));
     if (per_launch > 0x7fffffffull) per_launch = 0x7fffffffull;
     for (uint64_t t0 = t_lo; t0 < t_hi;) {
         uint64_t t1 = std::min(t_hi, t0 + per_launch);
@@ -592,7 +584,7 @@ void Engine::pfp_stream(ScanState& SS, const mmt_params& p) {
     hipStream_t st = stream_;
     const uint64_t ALIGN_R = 4096;
     uint64_t range = wide_ ? (1ull << 28) : std::min<uint64_t>(n, 1ull << 28);
-    if (const char* c = std::getenv("MMT_SCAN_RANGE")) range = std::max<uint64_t>(1, std::strtoull(c, nullptr, 10));
+    if (sw::is_set(sw::MMT_SCAN_RANGE)) range = std::max<uint64_t>(1, sw::num(sw::MMT_SCAN_RANGE, 0));
     range = (std::max<uint64_t>(range, 1) + ALIGN_R - 1) / ALIGN_R * ALIGN_R;
     uint64_t lo = 0, hi = n;
     shard_range(shard_index_, lo, hi);
@@ -622,12 +614,12 @@ void Engine::pfp_stream(ScanState& SS, const mmt_params& p) {
             pfp_emit_window(b0, c1, 0);
             ee.stop(st);
             stream_entries_ += len;
-            if (std::getenv("MMT_EMIT_ABLATE")) break;       // timing of a crippled emitter (tests/micro/emit_ablate.sh): its windows are garbage
+            if (sw::is_set(sw::MMT_EMIT_ABLATE)) break;       // timing of a crippled emitter (tests/micro/emit_ablate.sh): its windows are garbage
             if (hand_off_window(SS, 0, window_view(0, b0, (uint32_t)len, (uint32_t)ext), p, false)) break;
             ext = std::max<uint64_t>(ext * 4, SS.ext0);      // a walk ran off the extension
         }
     }
-    if (read_u32(S.err.get(), st) && !std::getenv("MMT_EMIT_ABLATE")) {
+    if (read_u32(S.err.get(), st) && !sw::is_set(sw::MMT_EMIT_ABLATE)) {
         std::vector<uint32_t> er;
         d2h(er, S.err.get(), 16, st);
         auto u64 = [&](int i) { return (unsigned long long)er[i] | ((unsigned long long)er[i + 1] << 32); };

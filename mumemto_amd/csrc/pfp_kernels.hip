@@ -202,7 +202,7 @@ void trigger_masks(const TextRef& text, uint64_t n, uint32_t w, uint32_t p, uint
     for (int i = 0; i < 5; i++) qinv *= 2u - q * qinv;
     const uint32_t qlim = 0xffffffffu / q;
     // (text.v = V: the text itself begins one byte on, 16-byte aligned -- Engine::text_ptr)
-    const bool fast = !getenv("MMT_TRIGGER_PLAIN") && (text.is_packed() || (reinterpret_cast<uintptr_t>(text.v + 1) & 15u) == 0);
+    const bool fast = !sw::on(sw::MMT_TRIGGER_PLAIN) && (text.is_packed() || (reinterpret_cast<uintptr_t>(text.v + 1) & 15u) == 0);
 #define MMT_TRIG(WW) for_trigger_slices(n, [&](uint32_t b0, uint32_t cnt) { \
         hipLaunchKernelGGL((k_trigger_masks_fast<256, WW>), dim3(cnt), dim3(256), 0, s, text, n, (uint32_t)pot, pe, qinv, qlim, \
                            masks, block_count, b0); })
@@ -1613,12 +1613,8 @@ __global__ __launch_bounds__(BLOCK, 7) void k_emit2(EmitArgsT<P, SA> a, const Em
 }
 
 uint32_t emit_tile() {
-    static const uint32_t t = [] {
-        const char* e = getenv("MMT_EMIT_TILE");
-        const int v = e ? atoi(e) : 896;
-        return (uint32_t)(v == 1024 || v == 768 ? v : 896);
-    }();
-    return t;
+    const int v = sw::num(sw::MMT_EMIT_TILE, 896);
+    return (uint32_t)(v == 1024 || v == 768 ? v : 896);
 }
 template <typename P, typename SA, int TILE, int BLOCK = 256>
 static void emit_typed(const EmitArgs& a, const uint32_t* tile_first_tab, uint64_t tile_base, void* plan, uint64_t tile_lo, uint64_t tile_hi, hipStream_t s) {
@@ -1634,22 +1630,20 @@ static void emit_typed(const EmitArgs& a, const uint32_t* tile_first_tab, uint64
     t.lcp = a.lcp; t.ghead = static_cast<const uint2*>(a.ghead); t.rmq = a.rmq; t.w = a.w;
     t.out_base = a.out_base; t.win_lo = a.win_lo; t.win_hi = a.win_hi;
     // (tests/micro: MMT_EMIT_MANY=0 sorts every piece, a large value none)
-    static const uint32_t many = std::getenv("MMT_EMIT_MANY") ? (uint32_t)std::atoi(std::getenv("MMT_EMIT_MANY")) : 24u;
-    t.many_runs = many;
-    static const uint32_t abl2 = std::getenv("MMT_EMIT2_ABLATE") ? (uint32_t)std::atoi(std::getenv("MMT_EMIT2_ABLATE")) : 0u;
-    t.abl2 = abl2;
+    t.many_runs = (uint32_t)sw::num(sw::MMT_EMIT_MANY, 24);
+    t.abl2 = (uint32_t)sw::num(sw::MMT_EMIT2_ABLATE, 0);
     const uint32_t n_tiles = (uint32_t)(tile_hi - tile_lo);
     EmitDesc* desc = static_cast<EmitDesc*>(plan);
     hipLaunchKernelGGL((k_emit_plan<P, TILE, CAP>), dim3(grid_for(n_tiles, 256)), dim3(256), 0, s, t.segb, t.sege, tile_first_tab,
                        tile_base, tile_lo, n_tiles, desc);
     // persistent workgroups: seven per CU (the launch bounds), a few rounds of them so that the tail is short
     // (MMT_EMIT_GRID: workgroups of the launch, tests/micro; 0 = one per tile)
-    static const uint32_t grid_env = std::getenv("MMT_EMIT_GRID") ? (uint32_t)std::atoi(std::getenv("MMT_EMIT_GRID")) : 256u * 7u * 4u;
+    const uint32_t grid_env = (uint32_t)sw::num(sw::MMT_EMIT_GRID, 256 * 7 * 4);
     const uint32_t grid = grid_env ? std::min(grid_env, n_tiles) : n_tiles;
     // MMT_EMIT_ABLATE (tests/micro/emit_ablate.sh, wide 896-element tiles only): the kernel with one of its phases cut out
     // -- WRONG OUTPUT, timing only -- 1 no column stores, 2 no merge ranks, 3 no occurrence records, 4 no group heads,
     // 5 nothing after the entry rows
-    static const int abl = std::getenv("MMT_EMIT_ABLATE") ? std::atoi(std::getenv("MMT_EMIT_ABLATE")) : 0;
+    const int abl = sw::num(sw::MMT_EMIT_ABLATE, 0);
     if constexpr (TILE == 896 && sizeof(P) == 8) {
         if (abl == 1) { hipLaunchKernelGGL((k_emit<BLOCK, CAP, TILE, P, SA, 1>), dim3(grid), dim3(BLOCK), 0, s, t, desc, n_tiles); return; }
         if (abl == 2) { hipLaunchKernelGGL((k_emit<BLOCK, CAP, TILE, P, SA, 2>), dim3(grid), dim3(BLOCK), 0, s, t, desc, n_tiles); return; }
@@ -1658,8 +1652,8 @@ static void emit_typed(const EmitArgs& a, const uint32_t* tile_first_tab, uint64
         if (abl == 5) { hipLaunchKernelGGL((k_emit<BLOCK, CAP, TILE, P, SA, 5>), dim3(grid), dim3(BLOCK), 0, s, t, desc, n_tiles); return; }
     }
     // MMT_EMIT_V1: the first form of the tile kernel (A/B, and the ablations above)
-    static const bool v1 = std::getenv("MMT_EMIT_V1") != nullptr;
-    if (v1 || (abl && !abl2)) hipLaunchKernelGGL((k_emit<BLOCK, CAP, TILE, P, SA>), dim3(grid), dim3(BLOCK), 0, s, t, desc, n_tiles);
+    const bool v1 = sw::on(sw::MMT_EMIT_V1);
+    if (v1 || (abl && !t.abl2)) hipLaunchKernelGGL((k_emit<BLOCK, CAP, TILE, P, SA>), dim3(grid), dim3(BLOCK), 0, s, t, desc, n_tiles);
     else hipLaunchKernelGGL((k_emit2<BLOCK, CAP, TILE, P, SA>), dim3(grid), dim3(BLOCK), 0, s, t, desc, n_tiles);
     MMT_HIP(hipGetLastError());
 }

@@ -52,11 +52,8 @@ std::mutex g_unmap_thread_mu;                       // guards g_unmap_thread its
 std::thread* g_unmap_thread = nullptr;
 
 bool enabled() {
-    static const bool on = [] {
-        const char* e = std::getenv("MUMEMTO_POOL");
-        return !(e && std::string(e) == "0");
-    }();
-    return on;
+    const char* e = sw::text(sw::MUMEMTO_POOL);
+    return !(e && std::string(e) == "0");
 }
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -118,7 +115,7 @@ void add_free(std::map<size_t, size_t>& fl, size_t off, size_t size) {
 }
 
 size_t heap_limit() {
-    static const size_t limit = [] { const char* e = std::getenv("MUMEMTO_HEAP_LIMIT"); return e ? (size_t)std::strtoull(e, nullptr, 10) : (size_t)0; }();
+    const size_t limit = (size_t)sw::num(sw::MUMEMTO_HEAP_LIMIT, 0);
     return limit;
 }
 
@@ -126,7 +123,7 @@ size_t heap_limit() {
 // (pool::available) know about it, unlike MUMEMTO_HEAP_LIMIT, which exists to make an accepted run fail
 std::atomic<size_t> g_reserve_set{~(size_t)0};        // pool::set_reserve (tests): overrides the environment while it is not ~0
 size_t driver_reserve() {
-    static const size_t keep = [] { const char* e = std::getenv("MUMEMTO_HEAP_RESERVE"); return e ? (size_t)std::strtoull(e, nullptr, 10) : (size_t)0; }();
+    const size_t keep = (size_t)sw::num(sw::MUMEMTO_HEAP_RESERVE, 0);
     const size_t set = g_reserve_set.load();
     return set != ~(size_t)0 ? set : keep;
 }

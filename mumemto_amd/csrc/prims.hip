@@ -314,6 +314,8 @@ __global__ void k_ranges_scatter(const K* __restrict__ gk, const V* __restrict__
     const uint32_t dst = begin[lo] + (c - off[lo]);
     kout[dst] = gk[c]; vout[dst] = gv[c];
 }
+// elements up to which the ranges are sorted as one (MMT_RANGES_AS_ONE_MAX: tuning aid)
+static uint64_t ranges_as_one_max() { return sw::num(sw::MMT_RANGES_AS_ONE_MAX, 400000000); }
 template <typename K, typename V>
 static bool sort_ranges_as_one(DevBuf<uint8_t>& temp, const K* kin, K* kout, const V* vin, V* vout,
                                std::vector<uint32_t>& hb, std::vector<uint32_t>& he, int end_bit, hipStream_t s) {
@@ -330,9 +332,7 @@ static bool sort_ranges_as_one(DevBuf<uint8_t>& temp, const K* kin, K* kout, con
         total += he[r] - hb[r];
     }
     tab[2 * (size_t)R] = (uint32_t)total;
-    static const uint64_t limit = std::getenv("MMT_RANGES_AS_ONE_MAX") ? std::strtoull(std::getenv("MMT_RANGES_AS_ONE_MAX"), nullptr, 10)
-                                                                      : (uint64_t)400000000ull;
-    if (total == 0 || total > limit) return false;
+    if (total == 0 || total > ranges_as_one_max()) return false;
     const uint32_t T = (uint32_t)total;
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t kb = up((size_t)T * sizeof(K)), vb = up((size_t)T * sizeof(V)), tb = up(tab.size() * 4);
@@ -402,9 +402,7 @@ static bool sort_ranges_as_one_tagged(DevBuf<uint8_t>& temp, const uint32_t* kin
         total += he[r] - hb[r];
     }
     tab[2 * (size_t)R] = (uint32_t)total;
-    static const uint64_t limit = std::getenv("MMT_RANGES_AS_ONE_MAX") ? std::strtoull(std::getenv("MMT_RANGES_AS_ONE_MAX"), nullptr, 10)
-                                                                      : (uint64_t)400000000ull;
-    if (total == 0 || total > limit) return false;
+    if (total == 0 || total > ranges_as_one_max()) return false;
     const uint32_t T = (uint32_t)total;
     int rbits = 1;
     while ((1ull << rbits) < (uint64_t)R) rbits++;
@@ -446,14 +444,14 @@ template <typename K, typename V>
 static void sort_ranges(DevBuf<uint8_t>& temp, const K* kin, K* kout, const V* vin, V* vout, uint32_t n,
                         uint32_t segments, const uint32_t* begin, const uint32_t* end, int end_bit, hipStream_t s,
                         bool keys_order_the_ranges = false) {
-    static const uint32_t GIANT = std::getenv("MMT_GIANT_RANGE") ? (uint32_t)std::atoi(std::getenv("MMT_GIANT_RANGE")) : 65536u;
+    const uint32_t GIANT = (uint32_t)sw::num(sw::MMT_GIANT_RANGE, 65536);
     if (!segments) return;
     std::vector<uint32_t> hb(segments), he(segments);
     MMT_HIP(hipMemcpyAsync(hb.data(), begin, (size_t)segments * 4, hipMemcpyDeviceToHost, s));
     MMT_HIP(hipMemcpyAsync(he.data(), end, (size_t)segments * 4, hipMemcpyDeviceToHost, s));
     MMT_HIP(hipStreamSynchronize(s));
     // (MMT_RANGES_AS_ONE=0: the older route -- a sort per giant range, a segmented sort for the rest --, A/B and tests)
-    static const bool as_one = !(std::getenv("MMT_RANGES_AS_ONE") && std::atoi(std::getenv("MMT_RANGES_AS_ONE")) == 0);
+    const bool as_one = sw::on(sw::MMT_RANGES_AS_ONE);
     if (keys_order_the_ranges && as_one && sort_ranges_as_one(temp, kin, kout, vin, vout, hb, he, end_bit, s)) return;
     if constexpr (sizeof(K) == 4) {
         // many ranges, or any range one workgroup would be busy with for long: one sort of tagged keys
@@ -465,7 +463,7 @@ static void sort_ranges(DevBuf<uint8_t>& temp, const K* kin, K* kout, const V* v
     // a range is "giant" when one workgroup would still be busy with it long after the other ranges, which share the
     // chip a few hundred at a time, are done: beyond GIANT elements and four times the 256th longest range
     uint32_t thresh = GIANT;
-    if (segments > 256 && !std::getenv("MMT_GIANT_RANGE")) {
+    if (segments > 256 && !sw::is_set(sw::MMT_GIANT_RANGE)) {
         std::vector<uint32_t> len(segments);
         for (uint32_t i = 0; i < segments; i++) len[i] = he[i] - hb[i];
         std::nth_element(len.begin(), len.begin() + 255, len.end(), std::greater<uint32_t>());
@@ -474,7 +472,7 @@ static void sort_ranges(DevBuf<uint8_t>& temp, const K* kin, K* kout, const V* v
     std::vector<uint32_t> giant, rb, re;
     for (uint32_t i = 0; i < segments; i++)
         if (he[i] - hb[i] > thresh) giant.push_back(i);
-    if (std::getenv("MMT_RANGE_STATS")) {                    // tuning aid
+    if (sw::on(sw::MMT_RANGE_STATS)) {                    // tuning aid
         uint64_t total = 0;
         uint32_t longest = 0;
         for (uint32_t i = 0; i < segments; i++) { total += he[i] - hb[i]; longest = std::max(longest, he[i] - hb[i]); }

@@ -34,7 +34,7 @@ void DoublingSorter::release() {
 }
 
 void DoublingSorter::sort_round(uint32_t m, int shift, DevBuf<uint8_t>& temp, hipStream_t s) {
-    static const bool global_sort = std::getenv("MMT_SORT_GLOBAL_ROUNDS") != nullptr;     // the old path (tests)
+    const bool global_sort = sw::on(sw::MMT_SORT_GLOBAL_ROUNDS);     // the old path (tests)
     if (global_sort || m < 4096) {
         prims::sort_pairs_u64_u32(temp, keys_a_.get(), keys_b_.get(), sac_a_.get(), sac_b_.get(), m, 0,
                                   std::min(64, 2 * shift), s);
@@ -69,8 +69,8 @@ void DoublingSorter::sort_round(uint32_t m, int shift, DevBuf<uint8_t>& temp, hi
 void DoublingSorter::refine_runs(uint32_t n, const RunRefine& R, uint32_t* sa, std::vector<uint32_t>& forced,
                                  DevBuf<uint8_t>& temp, hipStream_t s) {
     // (MMT_RUN_BUCKET: the smallest bucket that is worth a sort of its own; the tests lower it)
-    const uint32_t min_bucket = std::getenv("MMT_RUN_BUCKET") ? (uint32_t)std::atoi(std::getenv("MMT_RUN_BUCKET")) : 4096u;
-    const bool trace = std::getenv("MMT_SORT_TRACE") != nullptr;
+    const uint32_t min_bucket = (uint32_t)sw::num(sw::MMT_RUN_BUCKET, 4096);
+    const bool trace = sw::on(sw::MMT_SORT_TRACE);
     const int S = std::min(R.sigma, 15);
     std::vector<uint64_t> probe(S);
     for (int c = 1; c <= S; c++) {
@@ -103,14 +103,14 @@ int DoublingSorter::sort(uint32_t n, int key_bits, uint64_t h0, uint32_t* sa, ui
     prims::sort_pairs_u64_u32(temp, keys_a_.get(), keys_b_.get(), sac_a_.get(), sa, n, 0, std::min(64, key_bits), s);
     run_refined_ = 0;
     std::vector<uint32_t> forced;
-    if (runs && runs->n_ends && lsb_unique && !std::getenv("MMT_NO_RUN_REFINE")) refine_runs(n, *runs, sa, forced, temp, s);
+    if (runs && runs->n_ends && lsb_unique && !sw::on(sw::MMT_NO_RUN_REFINE)) refine_runs(n, *runs, sa, forced, temp, s);
     // the input keys are dead: their column holds the head marks and the index list; the sorted keys die with mark_heads:
     // their column holds the heads and the flags (n entries each, at fixed places, for every later round as well)
     uint32_t* const headval = reinterpret_cast<uint32_t*>(keys_a_.get());
     uint32_t* const idx = headval + n;
     uint32_t* const head = reinterpret_cast<uint32_t*>(keys_b_.get());
     uint8_t* const flags = reinterpret_cast<uint8_t*>(head + n);
-    if (!side_ && !std::getenv("MMT_SORT_ONE_STREAM")) {
+    if (!side_ && !sw::on(sw::MMT_SORT_ONE_STREAM)) {
         MMT_HIP(hipStreamCreateWithFlags(&side_, hipStreamNonBlocking));
         MMT_HIP(hipEventCreateWithFlags(&ev_main_, hipEventDisableTiming));
         MMT_HIP(hipEventCreateWithFlags(&ev_side_, hipEventDisableTiming));
@@ -131,7 +131,7 @@ int DoublingSorter::sort(uint32_t n, int key_bits, uint64_t h0, uint32_t* sa, ui
         MMT_HIP(hipEventRecord(ev_side_, side_));
     } else k::scatter_rank(sa, head, n, rank, s);
     // (MMT_SORT_FLAG_ARRAY: the byte-flag pass + the selection over it, the two steps this replaced)
-    static const bool flag_array = std::getenv("MMT_SORT_FLAG_ARRAY") != nullptr;
+    const bool flag_array = sw::on(sw::MMT_SORT_FLAG_ARRAY);
     if (flag_array) {
         k::flag_unsorted(head, n, flags, s);
         prims::select_indices(temp, flags, idx, count_.get(), n, s);
@@ -146,9 +146,8 @@ int DoublingSorter::sort(uint32_t n, int key_bits, uint64_t h0, uint32_t* sa, ui
     if (side_) MMT_HIP(hipStreamWaitEvent(s, ev_side_, 0));                            // the ranks are in place
 
     const int shift = bit_width_u64(n);            // second key component holds values 0..n
-    static const bool fused_ok = !std::getenv("MMT_SORT_GLOBAL_ROUNDS") &&
-                                 !(std::getenv("MMT_SORT_FUSED") && std::atoi(std::getenv("MMT_SORT_FUSED")) == 0);
-    static const bool trace = std::getenv("MMT_SORT_TRACE") != nullptr;      // tuning aid: the active set round by round
+    const bool fused_ok = !sw::on(sw::MMT_SORT_GLOBAL_ROUNDS) && sw::on(sw::MMT_SORT_FUSED);
+    const bool trace = sw::on(sw::MMT_SORT_TRACE);      // tuning aid: the active set round by round
     if (trace) std::fprintf(stderr, "[sort] n %u, tied after the first pass %u (h = %llu)\n", n, m, (unsigned long long)h0);
     bool side_busy = false;
     uint64_t h = h0;
@@ -169,8 +168,8 @@ int DoublingSorter::sort(uint32_t n, int key_bits, uint64_t h0, uint32_t* sa, ui
             uint8_t* const flags_w = hf_.get() + m4 * 4;
             // room for the list of long ranges (satellite content: thousands per round); MMT_BIG_CAP: a small list, so that the
             // round of separate kernels takes over after the fused pass has run (tests)
-            static const uint32_t big_cap_min = std::getenv("MMT_BIG_CAP") ? (uint32_t)std::max(1, std::atoi(std::getenv("MMT_BIG_CAP"))) : 65536u;
-            const uint32_t big_cap = std::getenv("MMT_BIG_CAP") ? big_cap_min : (uint32_t)std::max<size_t>(big_begin_.size(), big_cap_min);
+            const uint32_t big_cap = sw::is_set(sw::MMT_BIG_CAP) ? (uint32_t)std::max(1, sw::num(sw::MMT_BIG_CAP, 0))
+                                                                 : (uint32_t)std::max<size_t>(big_begin_.size(), 65536);
             big_begin_.ensure(big_cap); big_end_.ensure(big_cap);
             MMT_HIP(hipMemsetAsync(count_.get() + 1, 0, 4, s));
             MMT_HIP(hipMemsetAsync(tile_big_.get(), 0, (size_t)n_tiles + 1, s));
@@ -196,7 +195,7 @@ int DoublingSorter::sort(uint32_t n, int key_bits, uint64_t h0, uint32_t* sa, ui
                 }
                 // the scatter of the ranks (random stores: latency) runs beside the compaction of the list (streams):
                 // both read the sorted list, the compaction writes the other copies of its columns
-                static const bool all_ranks = std::getenv("MMT_SORT_ALL_RANKS") != nullptr;        // (A/B: every rank rewritten)
+                const bool all_ranks = sw::on(sw::MMT_SORT_ALL_RANKS);        // (A/B: every rank rewritten)
                 hipStream_t sb = s;
                 if (side_) {
                     MMT_HIP(hipEventRecord(ev_main_, s));

@@ -1,5 +1,5 @@
-"""GPU box helper: process start -> exit of mumemto_exec on the bench workload, with and without handing the free top of the
-device heap back while the run goes on (MUMEMTO_NO_EARLY_UNMAP=1).  usage: exit_ab.py [reps]"""
+"""GPU box helper: process start -> exit of mumemto_exec on the bench workload, the uploads overlapped with the reads or after
+them (handing the free top of the device heap back while the run goes on is opt-in: MUMEMTO_EARLY_UNMAP=1).  usage: exit_ab.py [reps]"""
 import os, subprocess, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from mumemto_amd import synth, build
@@ -10,7 +10,7 @@ for h, bases in synth.haplotypes_sparse(94, 64_000_000, 0.001, 3):
     p = os.path.join(d, "h%02d.fa" % h); synth.write_fasta_fast(p, bases, name="hap%03d" % h); paths.append(p)
 exe = os.path.join(os.path.dirname(build.LIB), "..", "bin", "mumemto_exec")
 for rep in range(reps):
-    for mode, env in (("upload overlapped", {"MUMEMTO_NO_EARLY_UNMAP": "1"}), ("upload after the reads", {"MUMEMTO_NO_EARLY_UNMAP": "1", "MUMEMTO_NO_UPLOAD_OVERLAP": "1"})):
+    for mode, env in (("upload overlapped", {}), ("upload after the reads", {"MUMEMTO_NO_UPLOAD_OVERLAP": "1"})):
         time.sleep(8)
         t = time.perf_counter()
         r = subprocess.run([exe, "-o", os.path.join(d, "out")] + paths, capture_output=True, text=True, env=dict(os.environ, MUMEMTO_TIMING="1", **env))

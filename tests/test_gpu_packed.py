@@ -237,9 +237,10 @@ def test_long_phrases_and_shared_variants_in_the_groups_of_copies(packed, copies
     try:
         with packed_env(MMT_PACKED_TEXT=packed):
             for w, p, no_rank in ((14, 157, 1), (10, 60, 0)):       # (MMT_GUIDED_NO_RANK: the records of a text beyond ~2^33 characters)
-                os.environ["MMT_GUIDED_NO_RANK"] = "1" if no_rank else "0"
-                if not no_rank:
-                    os.environ.pop("MMT_GUIDED_NO_RANK")
+                if no_rank:
+                    os.environ["MMT_GUIDED_NO_RANK"] = "1"       # (a presence switch: any value, "0" too, is on)
+                else:
+                    os.environ.pop("MMT_GUIDED_NO_RANK", None)
                 eng.set_producer("guided", w, p)
                 for kw in (dict(), dict(num_distinct=len(docs) - 1, max_doc_freq=3), dict(num_distinct=len(docs) // 2, max_doc_freq=2)):
                     eng.set_docs(docs)
