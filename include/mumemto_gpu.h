@@ -326,6 +326,34 @@ MMT_API int mmt_merged_blocks_device(const mmt_merged* m, const uint32_t** lr, c
  * column sorts, adjacency passes, blocks; [5] rows before, [6] rows kept, [7] columns that needed a sort, [8] columns found
  * ascending, [9] column batches, [10] 1 when the table itself was re-ordered, [11] blocks.                               */
 MMT_API int mmt_merged_collinear_stats(const mmt_merged* m, double out[12]);
+/* ---- inversion calls (`mumemto inversion`: mumemto/find_inversions.py find_reversals + inversion_coords) -----------------
+ * Callers detect these entry points by their symbols; mmt_abi_version() did not change for them.
+ * They work on the state mmt_merged_collinear leaves on the device: n full rows in ascending order of column 0 and blocks
+ * (first row, last row) in ascending order.  For every column i >= 1 the blocks are put into ascending order of the start of
+ * their first row in i (equal starts by block number, where the reference leaves the order to an unstable sort); a run is a
+ * maximal stretch of that order, at least two blocks, in which the block number falls by one from position to position.  A run
+ * is a call when every block of it lies on '-' in column i (one '+' block discards the whole run), and the call is
+ * (i, start, end, ref_start, ref_end): start = the start in i of the LAST row of the run's first block, end = the start in i
+ * of the FIRST row of its last block plus that row's length, ref_start / ref_end the same two rows in column 0.  Calls are in
+ * ascending order of (i, position of the run).  The tool runs mmt_merged_collinear(e, m, max_block_gap, -1, ...) first.
+ *
+ * mmt_merged_set_blocks attaches a block list read from a .bumbl file instead (lr: 2 x n_blocks host entries), the
+ * reference's "pre-computed collinear blocks".  It refuses, rc 3 and a message: a block out of range, with first > last, or
+ * blocks that are not ascending and disjoint; a table with a partial row; a table whose column 0 is not ascending.  The last
+ * two depart from the reference, which would compute on -1 starts.  From here on the text carries the fourth field.       */
+MMT_API int mmt_merged_set_blocks(mmt_engine* e, mmt_merged* m, const uint32_t* lr, uint64_t n_blocks);
+/* max_length >= 0 keeps the calls with |end - start| <= max_length only (negative: no limit).  Fails with a message when m
+ * carries no blocks.  Calling it again recomputes the calls; mmt_merged_collinear, mmt_merged_set_blocks and
+ * mmt_merged_sort_like_direct drop them.                                                                                */
+MMT_API int mmt_merged_inversions(mmt_engine* e, mmt_merged* m, int64_t max_length, uint64_t* n_calls);
+/* out receives 5 x n_calls host entries: column, start, end, ref_start, ref_end of every call                          */
+MMT_API int mmt_merged_inversion_calls(const mmt_merged* m, int64_t* out);
+/* the same values in HBM; owned by m                                                                                   */
+MMT_API int mmt_merged_inversion_calls_device(const mmt_merged* m, const int64_t** calls);
+/* Of the last mmt_merged_inversions on m: out[0..2] HIP-event milliseconds of the gather of the block heads, column sorts,
+ * run passes; [3] blocks, [4] columns that needed a sort, [5] columns skipped as ascending, [6] runs found before the strand
+ * and length filters, [7] calls.                                                                                        */
+MMT_API int mmt_merged_inversion_stats(const mmt_merged* m, double out[8]);
 /* Re-order merged rows into the order of a direct run (lexicographic by match
  * string) using the anchor suffix ranks of the engine's last run, whose
  * document 0 must be the anchor.                              */

@@ -15,6 +15,7 @@ from .binding import (  # noqa: F401
     collinear_blocks,
     Params,
     exchange_digest,
+    find_inversions,
     library_path,
     load_library,
     mumemto_mem,

@@ -82,7 +82,8 @@ GPU_ABI_SYMBOLS = [
     "mmt_dist_gather_text", "mmt_merged_write_text", "mmt_sort_pieces", "mmt_engine_keep_columns", "mmt_columns_kept",
     "mmt_comm_verify_stats", "mmt_exchange_digest", "mmt_exchange_digest_host", "mmt_stream_stats", "mmt_engine_release_columns", "mmt_copy_thresh32", "mmt_thresh_device32", "mmt_engine_set_text_sink",
     "mmt_engine_run_supplied", "mmt_merged_from_rows_device", "mmt_merged_collinear", "mmt_merged_blocks",
-    "mmt_merged_blocks_device", "mmt_merged_collinear_stats",
+    "mmt_merged_blocks_device", "mmt_merged_collinear_stats", "mmt_merged_set_blocks", "mmt_merged_inversions",
+    "mmt_merged_inversion_calls", "mmt_merged_inversion_calls_device", "mmt_merged_inversion_stats",
 ]
 
 
@@ -189,6 +190,11 @@ def load_library():
     L.mmt_merged_blocks.argtypes = [C.c_void_p, C.c_void_p]
     L.mmt_merged_blocks_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.mmt_merged_collinear_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    L.mmt_merged_set_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+    L.mmt_merged_inversions.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_uint64)]
+    L.mmt_merged_inversion_calls.argtypes = [C.c_void_p, C.c_void_p]
+    L.mmt_merged_inversion_calls_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.mmt_merged_inversion_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.mmt_comm_unique_id.argtypes = [C.c_void_p]
     L.mmt_comm_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
     L.mmt_comm_destroy.argtypes = [C.c_void_p]
@@ -884,6 +890,35 @@ class Merged:
                  batches=int(st[9]), table_sorted=bool(st[10]), n_blocks=int(st[11]))
         return d
 
+    def set_blocks(self, blocks):
+        """Attach a block list read from a file, (n_blocks, 2) first and last rows, as if collinear() had found it.  The table
+        must hold full rows only, in ascending order of column 0; a list that is not ascending and disjoint is refused."""
+        lr = np.ascontiguousarray(blocks, np.uint32).reshape(-1, 2)
+        _check(self.L.mmt_merged_set_blocks(self.engine.h, self.h, _p(lr) if len(lr) else None, len(lr)))
+
+    def inversions(self, max_length=None):
+        """Inversion calls as the reference's `mumemto inversion` finds them, over the blocks of collinear() or set_blocks():
+        int64 [k, 5] = (column, start, end, ref_start, ref_end) in ascending order of (column, position of the run)."""
+        k = C.c_uint64()
+        limit = -1 if max_length is None else int(max_length)
+        _check(self.L.mmt_merged_inversions(self.engine.h, self.h, C.c_int64(limit), C.byref(k)))
+        calls = np.zeros((int(k.value), 5), np.int64)
+        _check(self.L.mmt_merged_inversion_calls(self.h, _p(calls) if len(calls) else None))
+        return calls
+
+    def inversion_calls_device(self):
+        """address of the int64 [n_calls, 5] calls in HBM"""
+        a = C.c_void_p()
+        _check(self.L.mmt_merged_inversion_calls_device(self.h, C.byref(a)))
+        return a.value or 0
+
+    def inversion_stats(self):
+        st = (C.c_double * 8)()
+        _check(self.L.mmt_merged_inversion_stats(self.h, st))
+        d = {k: float(st[i]) for i, k in enumerate(["gather_ms", "sort_ms", "runs_ms"])}
+        d.update(n_blocks=int(st[3]), cols_sorted=int(st[4]), cols_ascending=int(st[5]), runs=int(st[6]), calls=int(st[7]))
+        return d
+
     def text(self):
         k = C.c_size_t()
         ptr = self.L.mmt_merged_text(self.h, C.byref(k))
@@ -903,6 +938,18 @@ def collinear_blocks(lengths, starts, strands, max_break=1000, min_singleton_len
             blocks = m.collinear(max_break, min_singleton_length)
             length, off, st = m.rows()
             return (length, off, st.astype(bool)), blocks
+    finally:
+        eng.close()
+
+
+def find_inversions(lengths, starts, strands, max_block_gap=1000, max_length=None, device=0):
+    """Rows on the host -> inversion calls int64 [k, 5] = (column, start, end, ref_start, ref_end): the collinear blocks of the
+    filtered, sorted table (no singletons), then the calls over them, all on the device."""
+    eng = Engine(device)
+    try:
+        with Merged.from_rows(eng, lengths, starts, strands) as m:
+            m.collinear(max_block_gap, None)
+            return m.inversions(max_length)
     finally:
         eng.close()
 

@@ -21,6 +21,7 @@
 #include "fasta.hpp"
 #include "merge.hpp"
 #include "collinear.hpp"
+#include "inversion.hpp"
 
 namespace {
 
@@ -101,6 +102,7 @@ struct mmt_merged {
     mmt::Engine* engine = nullptr;     // the engine whose device and stream the rows live on
     bool text_valid = false;
     mmt::CollinearStats coll;          // of the last mmt_merged_collinear
+    mmt::InversionStats inv;           // of the last mmt_merged_inversions
 };
 
 extern "C" {
@@ -781,6 +783,50 @@ int mmt_merged_collinear_stats(const mmt_merged* m, double out[12]) {
     for (int i = 0; i < 5; i++) out[i] = S.ms[i];
     out[5] = (double)S.rows_in; out[6] = (double)S.rows_kept; out[7] = (double)S.cols_sorted; out[8] = (double)S.cols_ascending;
     out[9] = (double)S.batches; out[10] = (double)S.table_sorted; out[11] = (double)m->rows.n_blocks;
+    return 0;
+}
+// ---- inversion calls (inversion.cpp) ---------------------------------------------------------
+int mmt_merged_set_blocks(mmt_engine* e, mmt_merged* m, const uint32_t* lr, uint64_t n_blocks) {
+    if (!e || !m) return fail(1, "engine and merged rows must be non-null");
+    if (e->e.get() != m->engine) return fail(1, "the merged rows belong to another engine");
+    MMT_TRY
+    mmt::set_blocks(*e->e, m->rows, lr, n_blocks);
+    m->text.clear(); m->text_valid = false;
+    MMT_CATCH
+}
+int mmt_merged_inversions(mmt_engine* e, mmt_merged* m, int64_t max_length, uint64_t* n_calls) {
+    if (!e || !m) return fail(1, "engine and merged rows must be non-null");
+    if (e->e.get() != m->engine) return fail(1, "the merged rows belong to another engine");
+    MMT_TRY
+    mmt::inversion_calls(*e->e, m->rows, max_length, &m->inv);
+    if (n_calls) *n_calls = m->rows.n_calls;
+    MMT_CATCH
+}
+int mmt_merged_inversion_calls(const mmt_merged* m, int64_t* out) {
+    if (!m) return fail(1, "null");
+    if (!m->rows.has_calls) return fail(3, "no inversion calls attached: call mmt_merged_inversions first");
+    MMT_TRY
+    if (m->rows.n_calls) {
+        if (!out) throw std::invalid_argument("out must hold 5 x n_calls entries");
+        hipStream_t st = m->engine->stream();
+        MMT_HIP(hipSetDevice(m->engine->device()));
+        MMT_HIP(hipMemcpyAsync(out, m->rows.d_calls.get(), m->rows.n_calls * 40, hipMemcpyDeviceToHost, st));
+        MMT_HIP(hipStreamSynchronize(st));
+    }
+    MMT_CATCH
+}
+int mmt_merged_inversion_calls_device(const mmt_merged* m, const int64_t** calls) {
+    if (!m) return fail(1, "null");
+    if (!m->rows.has_calls) return fail(3, "no inversion calls attached: call mmt_merged_inversions first");
+    if (calls) *calls = m->rows.d_calls.get();
+    return 0;
+}
+int mmt_merged_inversion_stats(const mmt_merged* m, double out[8]) {
+    if (!m || !out) return fail(1, "null");
+    const mmt::InversionStats& S = m->inv;
+    for (int i = 0; i < 3; i++) out[i] = S.ms[i];
+    out[3] = (double)S.blocks; out[4] = (double)S.cols_sorted; out[5] = (double)S.cols_ascending; out[6] = (double)S.runs;
+    out[7] = (double)(m->rows.has_calls ? m->rows.n_calls : 0);
     return 0;
 }
 int mmt_merged_sort_like_direct(mmt_engine* e, mmt_merged* m) {

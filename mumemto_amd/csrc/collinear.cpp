@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "collinear_kernels.hpp"
+#include "laps.hpp"
 #include "merge_kernels.hpp"
 #include "pool.hpp"
 #include "prims.hpp"
@@ -18,35 +19,6 @@ namespace mmt {
 namespace {
 
 int bit_width_u64(uint64_t v) { int b = 0; while (v) { b++; v >>= 1; } return b ? b : 1; }
-
-// HIP-event laps of the stages; the events are read at the points where the host waits for the stream anyway
-class Laps {
-public:
-    Laps(hipStream_t s, float* ms) : s_(s), ms_(ms) {}
-    ~Laps() { for (auto& l : open_) { (void)hipEventDestroy(l.a); (void)hipEventDestroy(l.b); } }
-    void begin(int stage) {
-        if (!ms_) return;
-        Lap l; l.stage = stage;
-        MMT_HIP(hipEventCreate(&l.a)); MMT_HIP(hipEventCreate(&l.b));
-        MMT_HIP(hipEventRecord(l.a, s_));
-        open_.push_back(l);
-    }
-    void end() { if (ms_) MMT_HIP(hipEventRecord(open_.back().b, s_)); }
-    void collect() {                                  // after a stream synchronisation
-        for (auto& l : open_) {
-            float t = 0.f;
-            MMT_HIP(hipEventElapsedTime(&t, l.a, l.b));
-            ms_[l.stage] += t;
-            (void)hipEventDestroy(l.a); (void)hipEventDestroy(l.b);
-        }
-        open_.clear();
-    }
-private:
-    struct Lap { hipEvent_t a, b; int stage; };
-    hipStream_t s_;
-    float* ms_;
-    std::vector<Lap> open_;
-};
 
 }  // namespace
 
@@ -64,6 +36,7 @@ void collinear_blocks(Engine& e, MergedRows& m, uint32_t max_break, int64_t min_
     S = CollinearStats();
     Laps laps(st, stats ? S.ms : nullptr);
     m.has_blocks = false; m.n_blocks = 0;
+    m.has_calls = false; m.n_calls = 0;
     S.rows_in = m.n_rows;
 
     // ---- (1) MUMdata.filter_pmums + MUMdata.sort (utils.py:486-495, :323-361) -------------------------------------------

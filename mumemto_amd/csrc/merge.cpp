@@ -454,6 +454,7 @@ void sort_like_direct(Engine& e, MergedRows& m) {
     m.d_length.swap(len2); m.d_offsets.swap(off2); m.d_strands.swap(st2);
     m.on_host = false;
     m.has_blocks = false; m.n_blocks = 0;       // (blocks are row ranges of the order they were computed in)
+    m.has_calls = false; m.n_calls = 0;
 }
 
 // the fourth field of the text: the collinear block of every row, when blocks are attached (collinear.hpp)

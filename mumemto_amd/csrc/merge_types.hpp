@@ -25,6 +25,10 @@ struct MergedRows {
     size_t n_blocks = 0;
     DevBuf<uint32_t> d_row_block;   // n_rows: block of the row, 0xFFFFFFFF = none
     DevBuf<uint32_t> d_blocks;      // n_blocks x (first row, last row)
+    // inversion calls (inversion.hpp) over those blocks, attached by inversion_calls(); whatever replaces the blocks drops them
+    bool has_calls = false;
+    size_t n_calls = 0;
+    DevBuf<int64_t> d_calls;        // n_calls x (column, start, end, ref_start, ref_end)
 
     MergedRows() = default;
     MergedRows(MergedRows&& o) noexcept { *this = std::move(o); }
@@ -35,6 +39,8 @@ struct MergedRows {
         thresh = std::move(o.thresh);
         has_blocks = o.has_blocks; n_blocks = o.n_blocks;
         d_row_block.swap(o.d_row_block); d_blocks.swap(o.d_blocks);
+        has_calls = o.has_calls; n_calls = o.n_calls;
+        d_calls.swap(o.d_calls);
         return *this;
     }
 };
