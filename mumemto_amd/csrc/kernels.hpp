@@ -71,6 +71,10 @@ void make_round_keys(const uint32_t* sa_c, const uint32_t* head_c, uint32_t m, c
 // bound[t] (n_tiles + 1 entries) = first bucket start at or after t * target, ROUND_NO_BOUND when none within
 // `limit` elements; round_local_sort sorts every range between consecutive bounds that fits ROUND_TILE_CAP
 // elements in LDS and lists the longer ones (begin, end) for a segmented radix sort.
+// The list of long ranges: *big_count counts them all; only the first big_cap slots are ever written (more than big_cap:
+// the list is incomplete and the caller sorts the round another way).  bound[t] == bound[t + 1]: tile t is empty.
+// round_fused expects the same of its list; it also relies on pos[c] - head_c[c] being element c's offset inside its
+// bucket (every member of a tied bucket is in the list, at consecutive positions).
 static const uint32_t ROUND_TILE_CAP = 2048;
 void round_tile_bounds(const uint64_t* keys, uint32_t m, int shift, uint32_t target, uint32_t limit, uint32_t n_tiles,
                        uint32_t* bound, hipStream_t s);

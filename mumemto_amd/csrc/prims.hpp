@@ -43,6 +43,10 @@ void segmented_sort_pairs_u32_u64vals_ranges(DevBuf<uint8_t>& temp, const uint32
                                              const uint32_t* end, int end_bit, hipStream_t s);
 
 // 64-bit keys, ranges [begin[i], end[i]) of one array; elements outside the ranges are not touched.
+// The ranges may be listed in any order, may be empty and may touch; every range is sorted by the key bits below end_bit and
+// the keys come back whole (the bits at and above end_bit are ignored by the order, never cleared).  Order among equal keys
+// is not specified.  Ranges that overlap: the one-sort routes decline them and the route behind sorts every range from the
+// input on its own, so the result is defined only where the overlapping ranges write the same (a range listed twice).
 // keys_order_the_ranges: every key of a range is above every key of the ranges that begin before it (the sorter's round keys
 // carry the bucket in their high bits): all ranges then go through ONE device-wide sort (prims.hip, sort_ranges_as_one)
 void segmented_sort_pairs_u64_ranges(DevBuf<uint8_t>& temp, const uint64_t* kin, uint64_t* kout, const uint32_t* vin,

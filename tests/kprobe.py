@@ -1,0 +1,528 @@
+"""ctypes / numpy side of tests/kprobe/libkprobe.so (single launch wrappers of the suffix sorter behind C functions),
+the plain references the kernel tests compare with, and the generator of legal active lists.
+
+Everything in the references is integer arithmetic on numpy arrays or Python ints: there is no tolerance anywhere.
+The references import nothing from the product; tests/test_sorter_reference_host.py checks them (and the generator)
+on the CPU, so that a broken reference cannot make a GPU test pass vacuously.
+"""
+import contextlib
+import ctypes
+import os
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(HERE, "kprobe", "libkprobe.so")
+NO_SEP = 0xFFFFFFFF
+NO_BOUND = 0xFFFFFFFF
+U32, U64, U8 = np.uint32, np.uint64, np.uint8
+SENT32 = 0xA5A5A5A5            # fill patterns of in/out arrays: what a wrapper must not touch comes back as this
+SENT64 = 0xA5A5A5A5A5A5A5A5
+SENT8 = 0xA5
+
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        _lib = ctypes.CDLL(LIB_PATH)
+        _lib.kp_last_error.restype = ctypes.c_char_p
+        _lib.kp_round_fused_cap.restype = ctypes.c_uint32
+        _lib.kp_round_tile_cap.restype = ctypes.c_uint32
+    return _lib
+
+
+class ProbeError(RuntimeError):
+    pass
+
+
+def _arg(a):
+    if isinstance(a, np.ndarray):
+        assert a.flags["C_CONTIGUOUS"]
+        return a.ctypes.data_as(ctypes.c_void_p)
+    if a is None:
+        return ctypes.c_void_p(0)
+    return a
+
+
+def call(name, *args):
+    """kp_<name>(*args): numpy arrays go as pointers, Python ints as 32-bit values (ctypes' default), None as NULL."""
+    fn = getattr(lib(), "kp_" + name)
+    rc = fn(*[_arg(a) for a in args])
+    if rc != 0:
+        raise ProbeError("kp_%s: %s" % (name, lib().kp_last_error().decode()))
+
+
+@contextlib.contextmanager
+def environment(**values):
+    """environment variables for the calls inside the block (live switches are read at every call), then as they were"""
+    old = {k: os.environ.get(k) for k in values}
+    os.environ.update(values)
+    try:
+        yield
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def u32(x):
+    return np.ascontiguousarray(x, dtype=U32)
+
+
+def u64(x):
+    return np.ascontiguousarray(x, dtype=U64)
+
+
+def u8(x):
+    return np.ascontiguousarray(x, dtype=U8)
+
+
+def c_u32(v):
+    return ctypes.c_uint32(int(v) & 0xFFFFFFFF)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# thin wrappers (shapes and sentinels in one place)
+# ---------------------------------------------------------------------------------------------------------------------
+def pack_keys(text, code, bits, chars, sep_code=NO_SEP, run_alloc=0, run_cap=0):
+    text = u8(text); n = len(text)
+    keys = np.empty(n, U64); vals = np.empty(n, U32)
+    if run_alloc:
+        ends = np.full(run_alloc, SENT32, U32); cnt = np.zeros(1, U32)
+        call("pack_keys", text, n, u8(code), bits, chars, c_u32(sep_code), keys, vals, ends, run_alloc, cnt, run_cap)
+        return keys, vals, ends, int(cnt[0])
+    call("pack_keys", text, n, u8(code), bits, chars, c_u32(sep_code), keys, vals, None, 0, None, 0)
+    return keys, vals
+
+
+def pack_keys_u32(parse, bits, chars):
+    parse = u32(parse); m = len(parse)
+    keys = np.empty(m, U64); vals = np.empty(m, U32)
+    call("pack_keys_u32", parse, m, bits, chars, keys, vals)
+    return keys, vals
+
+
+def scan(which, a, out_dtype):
+    a = np.ascontiguousarray(a); out = np.empty(len(a), out_dtype)
+    call("scan", which, a, out, len(a))
+    return out
+
+
+def sort_ranges(kin, vin, begin, end, end_bit, ordered=False):
+    """(kout, vout), both pre-filled with the sentinel pattern"""
+    kin = np.ascontiguousarray(kin); vin = np.ascontiguousarray(vin)
+    kout = np.full(len(kin), SENT64 if kin.itemsize == 8 else SENT32, kin.dtype)
+    vout = np.full(len(vin), SENT64 if vin.itemsize == 8 else SENT32, vin.dtype)
+    call("sort_ranges", kin.itemsize, vin.itemsize, kin, vin, kout, vout, len(kin), len(begin), u32(begin), u32(end), end_bit,
+         1 if ordered else 0)
+    return kout, vout
+
+
+def sorter_text(text, code, bits, chars, sigma, sep_code=NO_SEP, use_runs=False):
+    text = u8(text); n = len(text)
+    sa = np.empty(n, U32); rank = np.empty(n, U32); out = np.zeros(2, U64)
+    call("sorter_text", text, n, u8(code), bits, chars, sigma, c_u32(sep_code), 1 if use_runs else 0, sa, rank, out)
+    return sa, rank, int(out[0]), int(out[1])
+
+
+def sorter_ints(parse, bits, chars):
+    parse = u32(parse); m = len(parse)
+    sa = np.empty(m, U32); rank = np.empty(m, U32); out = np.zeros(2, U64)
+    call("sorter_ints", parse, m, bits, chars, sa, rank, out)
+    return sa, rank, int(out[0])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# references: first keys
+# ---------------------------------------------------------------------------------------------------------------------
+def bit_width(v):
+    return int(v).bit_length()
+
+
+def ref_pack_keys(sym, bits, chars, sep_code=NO_SEP):
+    """sym: symbol codes of the text.  key[i] = the first `chars` symbols of suffix i, big-endian, 0 past the end.  With a
+    separator: (symbols up to and including the first separator of the window, zero behind it) << 1 | 1, else key << 1."""
+    n = len(sym)
+    s = [int(x) for x in sym] + [0] * (chars + 1)
+    keys = np.empty(n, U64)
+    for i in range(n):
+        k = 0
+        hit = False
+        for c in range(chars):
+            x = 0 if hit else s[i + c]
+            k = (k << bits) | x
+            if not hit and sep_code != NO_SEP and s[i + c] == sep_code:
+                hit = True
+        if sep_code != NO_SEP:
+            k = (k << 1) | (1 if hit else 0)
+        keys[i] = k
+    return keys
+
+
+def ref_pack_keys_u32(parse, bits, chars):
+    m = len(parse)
+    s = [int(x) for x in parse] + [0] * chars
+    keys = np.empty(m, U64)
+    for i in range(m):
+        k = 0
+        for c in range(chars):
+            k = (k << bits) | s[i + c]
+        keys[i] = k
+    return keys
+
+
+def ref_run_ends(sym, chars):
+    """last positions of the maximal runs of `chars` or more equal non-zero symbols"""
+    out = []
+    n = len(sym)
+    i = 0
+    while i < n:
+        j = i
+        while j + 1 < n and sym[j + 1] == sym[i]:
+            j += 1
+        if sym[i] != 0 and j - i + 1 >= chars:
+            out.append(j)
+        i = j + 1
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# references: heads and ranks (the one-line definitions of kernels.hpp)
+# ---------------------------------------------------------------------------------------------------------------------
+def ref_mark_heads(keys, lsb_unique):
+    keys = u64(keys); n = len(keys)
+    j = np.arange(n, dtype=U32)
+    is_head = np.ones(n, bool)
+    is_head[1:] = keys[1:] != keys[:-1]
+    if lsb_unique:
+        is_head |= (keys & U64(1)) == 1
+    return np.where(is_head, j, U32(0)).astype(U32)
+
+
+def ref_running_max(a):
+    return np.maximum.accumulate(np.asarray(a))
+
+
+def ref_flag_unsorted(head):
+    head = u32(head); n = len(head)
+    own = head == np.arange(n, dtype=U32)
+    nxt = np.ones(n, bool)
+    nxt[:-1] = own[1:]
+    return (~(own & nxt)).astype(U8)
+
+
+def ref_mark_subheads(keys, pos):
+    keys = u64(keys); m = len(keys)
+    is_head = np.ones(m, bool)
+    is_head[1:] = keys[1:] != keys[:-1]
+    return np.where(is_head, u32(pos), U32(0)).astype(U32)
+
+
+def ref_round_flags(newhead, pos):
+    """flags[c] = 0 iff element c is a bucket of its own: newhead[c] == pos[c] and the next element (if any) is a head"""
+    newhead = u32(newhead); pos = u32(pos); m = len(pos)
+    own = newhead == pos
+    nxt = np.ones(m, bool)
+    nxt[:-1] = own[1:]
+    return (~(own & nxt)).astype(U8)
+
+
+def ref_round_keys(sac, headc, rank, n, h, shift):
+    """keys[c] = head[c] << shift | (rank[sa[c] + h] + 1, or 0 past the end); Python ints: no width to overflow"""
+    out = np.empty(len(sac), U64)
+    for c in range(len(sac)):
+        i = int(sac[c]) + int(h)
+        second = int(rank[i]) + 1 if i < n else 0
+        out[c] = ((int(headc[c]) << shift) | second) & 0xFFFFFFFFFFFFFFFF
+    return out
+
+
+def ref_equal_range(sorted_keys, probe):
+    s = [int(x) for x in sorted_keys]
+    out = []
+    for p in probe:
+        p = int(p)
+        out += [sum(1 for x in s if x < p), sum(1 for x in s if x <= p)]
+    return u32(out)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the generator of legal active lists
+# ---------------------------------------------------------------------------------------------------------------------
+class ActiveList:
+    """The input of a doubling round: m tied suffixes grouped by bucket.  pos[c] = suffix-array position (ascending),
+    sac[c] = the suffix there, headc[c] = position of its bucket's first element (head <= pos, a bucket's positions are
+    consecutive), rank = the rank column (rank[sa[j]] = head of j's bucket; a position outside every bucket is a
+    bucket of its own), sa = the suffix array so far, n its length."""
+
+    def __init__(self, sizes, gaps, tail=0, seed=1):
+        assert len(sizes) == len(gaps) and all(s >= 2 for s in sizes) and all(g >= 0 for g in gaps)
+        rng = np.random.default_rng(seed)
+        pos, headc = [], []
+        head_of = []
+        cur = 0
+        for s, g in zip(sizes, gaps):
+            head_of += list(range(cur, cur + g))
+            cur += g
+            pos += list(range(cur, cur + s)); headc += [cur] * s
+            head_of += [cur] * s
+            cur += s
+        head_of += list(range(cur, cur + tail))
+        self.n = cur + tail
+        self.m = len(pos)
+        self.sizes = list(sizes)
+        self.pos = u32(pos); self.headc = u32(headc)
+        self.sa = u32(rng.permutation(self.n))
+        self.head = u32(head_of)
+        self.sac = self.sa[self.pos]
+        self.rank = np.empty(self.n, U32)
+        self.rank[self.sa] = self.head
+        self.shift = bit_width(self.n)
+
+    def check(self):
+        n, m = self.n, self.m
+        assert m == sum(self.sizes) and len(self.pos) == m and len(self.sac) == m and len(self.headc) == m
+        assert np.all(self.pos[1:] > self.pos[:-1]) and (m == 0 or int(self.pos[-1]) < n)
+        assert np.all(self.headc <= self.pos)
+        assert sorted(self.sa.tolist()) == list(range(n))
+        assert np.array_equal(self.sac, self.sa[self.pos])
+        assert np.array_equal(self.rank[self.sac], self.headc)
+        c = 0
+        for s in self.sizes:                               # buckets contiguous, in order, head = first position
+            assert np.all(self.headc[c:c + s] == self.pos[c]) and np.array_equal(self.pos[c:c + s], self.pos[c] + np.arange(s, dtype=U32))
+            if c:
+                assert self.headc[c] != self.headc[c - 1]
+            c += s
+        assert np.array_equal(ref_flag_unsorted(self.head)[self.pos], np.ones(m, U8))       # every member is tied
+        assert int(ref_flag_unsorted(self.head).sum()) == m                                   # and nothing else is
+        return True
+
+
+def round_shapes(cap):
+    """The bucket lists the issue names, for a tile capacity `cap` (target = cap / 2): name -> (sizes, gaps, tail)."""
+    t = cap // 2
+    few = [2, 3, 5, 2, 7, 2]
+    return {
+        "short_edge": ([2, 128, 129, 2, 128, 2] + few, [1, 0, 3, 0, 0, 2] + [1] * len(few), 5),
+        "target_edge": ([t - 1, t, t + 1, 2, t, t - 1, 3], [0, 1, 0, 0, 2, 0, 0], 1),
+        "cap_edge": ([cap - 1, 2, cap, 3, cap + 1, 2, 2], [0, 0, 1, 0, 0, 0, 4], 2),
+        "four_tiles": ([3, 5 * t + 7, 2, 2], [0, 2, 0, 1], 3),           # four whole tiles inside: three bounds in a row are "none"
+        "ends_at_m": ([5, t + 9, 4 * t], [1, 0, 0], 0),                    # the last bucket ends exactly at m (= n)
+        "last_tile_one_bucket": ([2] * (t // 2) + [t - 3], [0] * (t // 2) + [0], 0),
+        "many_long": ([cap + 1, 2, cap + 5, cap + 2, 3, 2 * cap + 1], [0, 0, 0, 1, 0, 0], 0),
+    }
+
+
+def ref_bounds(headc, target, limit, n_tiles):
+    """bound[t] = first bucket start at or after t * target, NO_BOUND when none within `limit` elements; bound[0] = 0,
+    bound[n_tiles] = m; a start at or beyond m reads m"""
+    headc = u32(headc); m = len(headc)
+    start = np.ones(m, bool)
+    start[1:] = headc[1:] != headc[:-1]
+    starts = np.flatnonzero(start)
+    out = np.empty(n_tiles + 1, U32)
+    for t in range(n_tiles + 1):
+        if t == 0:
+            out[t] = 0
+        elif t == n_tiles:
+            out[t] = m
+        else:
+            c0 = t * target
+            stop = min(c0 + limit, m)
+            k = np.searchsorted(starts, c0)
+            c = int(starts[k]) if k < len(starts) else m
+            if c >= stop:
+                out[t] = m if stop >= m else NO_BOUND
+            else:
+                out[t] = c
+    return out
+
+
+def ref_ranges(bound, cap):
+    """the ranges between consecutive bounds: [(tile, end tile, begin, end, long)] of the non-empty ones"""
+    out = []
+    n_tiles = len(bound) - 1
+    for t in range(n_tiles):
+        b = int(bound[t])
+        if b == NO_BOUND:
+            continue
+        u = t + 1
+        while int(bound[u]) == NO_BOUND:
+            u += 1
+        e = int(bound[u])
+        if e > b:
+            out.append((t, u, b, e, e - b > cap))
+    return out
+
+
+def ref_tile_big(bound, cap):
+    n_tiles = len(bound) - 1
+    marks = np.zeros(n_tiles + 1, U8)
+    for t, u, b, e, long_ in ref_ranges(bound, cap):
+        if long_:
+            for x in range(t, u):
+                marks[x] = 1 | (2 if x == t else 0) | (4 if x + 1 == u else 0)
+    return marks
+
+
+def ref_round(al, h):
+    """One doubling round of the whole list: (sorted keys, new heads, flags, per element the (key -> set of suffixes))."""
+    keys = ref_round_keys(al.sac, al.headc, al.rank, al.n, h, al.shift)
+    order = np.argsort(keys, kind="stable")
+    ks = keys[order]
+    # buckets are contiguous and their heads ascend, so the global order by key keeps every bucket in its slots
+    newhead = ref_running_max(ref_mark_subheads(ks, al.pos)).astype(U32)
+    return keys, ks, al.sac[order], newhead, ref_round_flags(newhead, al.pos)
+
+
+def same_sets_per_run(keys_sorted, got_vals, want_vals, lo=0, hi=None):
+    """values compared as sets per run of equal keys (order among equal keys is not specified)"""
+    hi = len(keys_sorted) if hi is None else hi
+    c = lo
+    while c < hi:
+        d = c
+        while d + 1 < hi and keys_sorted[d + 1] == keys_sorted[c]:
+            d += 1
+        if sorted(np.asarray(got_vals[c:d + 1]).tolist()) != sorted(np.asarray(want_vals[c:d + 1]).tolist()):
+            return False
+        c = d + 1
+    return True
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# reference suffix sort (prefix doubling in numpy) and the inputs of the three call forms
+# ---------------------------------------------------------------------------------------------------------------------
+def ref_suffix_array(sym, terminator=None):
+    """Suffix array of the integer string `sym`; past the end sorts smallest.  terminator: every occurrence of that symbol
+    is unique, ordered by position (nothing behind a terminator is ever compared)."""
+    sym = np.asarray(sym, dtype=np.int64)
+    n = len(sym)
+    if n == 0:
+        return np.zeros(0, U32)
+    if terminator is not None:
+        is_t = sym == terminator
+        t_count = int(is_t.sum())
+        below = sym < terminator
+        s2 = np.where(below, sym, sym + t_count)         # room for t_count distinct terminators at the terminator's place
+        s2[is_t] = terminator + np.arange(t_count)
+        sym = s2
+    _, rank = np.unique(sym, return_inverse=True)
+    rank = rank.astype(np.int64) + 1
+    h = 1
+    while True:
+        second = np.zeros(n, np.int64)
+        if h < n:
+            second[:n - h] = rank[h:]
+        order = np.lexsort((second, rank))
+        r1, r2 = rank[order], second[order]
+        new = np.ones(n, np.int64)
+        new[1:] = (r1[1:] != r1[:-1]) | (r2[1:] != r2[:-1])
+        dense = np.cumsum(new)
+        rank = np.empty(n, np.int64)
+        rank[order] = dense
+        if dense[-1] == n:
+            return order.astype(U32)
+        h *= 2
+        assert h < 4 * n
+
+
+def naive_suffix_array(sym, terminator=None):
+    """sorted() on slices (n <= 2000): the check of ref_suffix_array"""
+    s = [int(x) for x in sym]
+    if terminator is not None:
+        def key(i):
+            out = []
+            for j in range(i, len(s)):
+                if s[j] == terminator:
+                    out.append((s[j], j))
+                    break
+                out.append((s[j], -1))
+            return out
+        return u32(sorted(range(len(s)), key=key))
+    return u32(sorted(range(len(s)), key=lambda i: s[i:]))
+
+
+def fibonacci_string(n):
+    a, b = "b", "a"
+    while len(b) < n:
+        a, b = b, b + a
+    return b[:n]
+
+
+def thue_morse(n):
+    return "".join("ab"[bin(i).count("1") & 1] for i in range(n))
+
+
+def text_inputs(n, seed=7):
+    """name -> bytes of length n over letters (byte values >= 65)"""
+    rng = np.random.default_rng(seed + n)
+    out = {
+        "a^n": "a" * n,
+        "(ab)^n": ("ab" * n)[:n],
+        "(abc)^n+x": (("abc" * n)[:max(n - 1, 0)] + "d")[:n],
+        "fibonacci": fibonacci_string(n),
+        "thue_morse": thue_morse(n),
+        "random2": "".join("ac"[x] for x in rng.integers(0, 2, n)),
+        "random4": "".join("acgt"[x] for x in rng.integers(0, 4, n)),
+    }
+    runs = []
+    while sum(len(r) for r in runs) < n:
+        runs.append("n" * int(rng.integers(50, 5001)) + "acgt"[int(rng.integers(0, 4))])
+    out["runs"] = "".join(runs)[:n]
+    return {k: np.frombuffer(v.encode(), U8).copy() for k, v in out.items()}
+
+
+PERIODIC_AND_RUNS = ("a^n", "(ab)^n", "(abc)^n+x", "runs")
+
+
+def byte_form(text):
+    """the engine's call form: dense codes of the bytes that occur, 0 = past the end"""
+    hist = np.bincount(text, minlength=256)
+    code = np.zeros(256, U8)
+    sigma = 0
+    for c in range(256):
+        if hist[c]:
+            sigma += 1
+            code[c] = sigma
+    bits = max(1, bit_width(sigma))
+    return code, bits, min(64 // bits, 64), sigma
+
+
+def dict_form(text, phrase=997):
+    """the dictionary's call form: the text cut into phrases ending in 0x01, the last byte 0x00; both share code 0 with
+    the padding and are unique terminators; byte 2 always has a code"""
+    t = text.tolist()
+    out = []
+    for i, x in enumerate(t):
+        out.append(x)
+        if (i + 1) % phrase == 0:
+            out.append(1)
+    d = u8(out[:max(len(t) - 1, 0)] + [0]) if len(t) else u8([])
+    hist = np.bincount(d, minlength=256)
+    code = np.zeros(256, U8)
+    sigma = 0
+    for c in range(2, 256):
+        if hist[c] or c == 2:
+            sigma += 1
+            code[c] = sigma
+    bits = max(1, bit_width(sigma))
+    return d, code, bits, min(63 // bits, 63), sigma
+
+
+def int_form(sym):
+    """the parse's call form: symbols 1 .. D, bits = bit_width(D), chars = 64 / bits"""
+    d = int(max(sym)) if len(sym) else 1
+    bits = max(1, bit_width(d))
+    return bits, max(1, 64 // bits)
+
+
+def round_bound(n, h0):
+    """ceil(log2(n / h0)) + 1 rounds at the most (a round with step h orders by 2 h characters; n distinguish all)"""
+    r = 0
+    while h0 * (1 << r) < n:
+        r += 1
+    return r + 1
