@@ -83,11 +83,16 @@ __device__ __forceinline__ uint32_t rmq_min8(const RmqView& R, uint32_t a, uint3
 }
 
 // block minima over 64 entries + sparse table over the blocks of any array of m values (bmin: levels * nb entries)
+// Contract: nb = ceil(m / 64), levels = the smallest L >= 1 with 2^L > nb; bmin[k * nb + b] = minimum of vals over blocks
+// [b, b + 2^k), entries and blocks past the end counting as 0xffffffff (such ranges are never queried).  m >= 1.
 void build_rmq(const uint32_t* vals, uint32_t m, DevBuf<uint32_t>& bmin, uint32_t& nb, uint32_t& levels, hipStream_t s);
 
 struct ParseLcp {
     DevBuf<uint32_t> sl, bmin;
     uint32_t m = 0, nb = 0, levels = 0;
+    // n_irreducible: entries r >= 1 that were compared directly; n_long: those of them that share CMP_STEPS x 64 = 512
+    // characters and have room for more (finished by k::long_lcp_dst).  sl[r] is, for EVERY r >= 1, the number of equal
+    // characters of V from pstart[sa_p[r]] and from pstart[sa_p[r - 1]], at most nv - the larger start and at most LCP_CAP.
     uint32_t n_irreducible = 0, n_long = 0;
     RmqView view() const { RmqView v; v.sl = sl.get(); v.bmin = bmin.get(); v.m = m; v.nb = nb; return v; }
     void release() { sl.release(); bmin.release(); m = nb = levels = 0; }

@@ -26,6 +26,14 @@ inline uint64_t kr_window_of_run(uint8_t c, uint32_t w) {
 
 // trigger positions in two passes: 16-bit masks (one per 16 text positions) + triggers per workgroup; then, given the
 // exclusive scan of those counts, the positions themselves (ascending)
+// Contract (tests/pfpmodel.py restates it): position i is a trigger iff i + 1 >= w and h_i % p == 0, h_i = sum_{k < w}
+// T[i - k] 256^k mod KR_PRIME with T[< 0] = 0; 1 <= w <= 32, p >= 1, n >= 1.  masks: ceil(n / 16) entries (bit q of masks[t] =
+// position 16 t + q; no bit at or behind n), block_count: trigger_blocks(n) entries (one workgroup = 256 masks = 4096
+// positions); nothing else is written.  A byte text whose first character (v + 1) is not 16-byte aligned, any w that has no
+// instantiation of the fast kernel and MMT_TRIGGER_PLAIN take the generic kernel: same result.
+// trigger_cuts: block_off = exclusive sum of block_count; writes cuts[0 .. sum of block_count) and nothing behind.
+// phrase_bounds: n_cuts + 1 phrases, phrase k = V[start[k], start[k] + len[k]) from the window of cut k - 1 (V index 0 for k = 0)
+// up to and including the window of cut k (the last: the w Dollars behind the text); a phrase has fewer than 2^32 characters.
 uint32_t trigger_blocks(uint64_t n);
 void trigger_masks(const TextRef& text, uint64_t n, uint32_t w, uint32_t p, uint16_t* masks, uint32_t* block_count,
                    hipStream_t s);
@@ -34,6 +42,13 @@ void phrase_bounds(const void* cuts, uint32_t n_cuts, uint64_t n, uint32_t w, vo
                    hipStream_t s);
 // h1: first fingerprint per phrase; pinfo: 16-byte record per phrase (56 bits of the second fingerprint, start (40
 // bits), length)
+// Contract: f_B(phrase) = sum (byte + 1) B^(len - 1 - i) mod 2^64; h1 = f_B1 ^ (len * 0xD6E8FEB86659FD93), g2 = f_B2 + (len << 32);
+// record = (g2 low word, bits 32..55 of g2 | (start >> 32) << 24, start low word, len).  Equal phrases get equal h1 and
+// equal (g2, len) fields wherever they stand.  The phrases must be those of a parse: consecutive in V, starts and ends
+// ascending (a whole wave stages the span of its 64 phrases in LDS), V readable for 16 bytes behind the last phrase.
+// mark_distinct: flags[0] = 1; flags[k] = 0 iff h1s[k] == h1s[k - 1], the (g2, len) fields of order[k] and order[k - 1] are
+// equal AND so are the bytes; err[0] += 1 for every k whose fields agree and whose bytes differ (two different phrases
+// that collide in both fingerprints: they stay apart), err[1] |= 1 when h1s[k] == h1s[k - 1] and the fields differ.
 void phrase_hash(const TextRef& v, const void* start, const uint32_t* len, uint32_t m, uint64_t* h1, void* pinfo,
                  bool wide, hipStream_t s);
 void second_fingerprint(const void* pinfo, uint32_t m, uint64_t* h2, hipStream_t s);
@@ -43,6 +58,8 @@ void assign_distinct(const uint32_t* order, const uint32_t* scan, const uint32_t
                      uint32_t m, uint32_t* pid, uint32_t* rep, uint32_t* dlen, hipStream_t s);
 // *d_out = x[0] + ... + x[n - 1] in 64 bits
 void sum_u32(const uint32_t* x, uint32_t n, uint64_t* d_out, hipStream_t s);
+// copy_dict: phrase which[d] goes to dict[dstart[d] ..), 0x01 behind it, 0x00 at dict[dict_len - 1]; a phrase that would not end
+// before the last byte (dstart + len >= dict_len) is left out entirely.  dinfo (may be null): see pfp_kernels.hip.
 void copy_dict(const TextRef& v, const void* start, const uint32_t* len, const uint32_t* which,
                const uint32_t* dstart, uint32_t n_phr, uint8_t* dict, uint64_t* dinfo, uint32_t dict_len,
                bool pack_prev, bool wide, hipStream_t s);
@@ -69,6 +86,8 @@ void phrase_table(const uint32_t* occ_start /* n_distinct + 1 */, const uint32_t
 void occ_sequence(const uint32_t* sa_p, const uint32_t* pid, uint32_t m, uint32_t D, uint32_t* keys, uint32_t* vals,
                   hipStream_t s);
 // occ_sl[k] = sl[t - 1] of the same occurrence (sl: parse_lcp.hpp), 0 for t = 0
+// (ids / ts: the m + 1 pairs of occ_sequence sorted stably by id -- the dummy id D is the largest, so its pair is entry m;
+// occ_start[id] is written for the ids that occur, occ_start[D] = m)
 void occ_finish(const uint32_t* ids, const uint32_t* ts, const uint32_t* sa_p, const void* pstart, uint32_t m,
                 uint32_t* occ_start, uint64_t* occ, uint32_t pos_bits, const uint32_t* sl, uint32_t* occ_sl, bool wide,
                 hipStream_t s);
@@ -130,7 +149,8 @@ struct EmitArgs {
 };
 struct BwtDecode { uint8_t byte[16]; };       // code -> byte
 // tile_first[t] = first group whose begin offset is >= t * EMIT_TILE (tiles + 1 entries, tiles = ceil(n_out / TILE))
-// (tile_base: the table begins at that tile -- entry t - tile_base --: the tables of one batch)
+// (tile_base: the table begins at that tile -- entry t - tile_base --: the tables of one batch; every group begins at or
+// behind tile tile_base - 1: segb[g] / TILE + 1 >= tile_base)
 void tile_first(const void* segb, uint32_t n_groups, uint64_t tiles, uint32_t* out, bool wide, hipStream_t s, uint64_t tile_base = 0);
 // output tiles [tile_lo, tile_hi); plan: emit_plan_bytes(tile_hi - tile_lo) bytes of device scratch (one record per tile,
 // written by a pre-pass of the launch: what a workgroup needs to know about a tile before it can load anything of it)

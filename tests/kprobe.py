@@ -1,5 +1,6 @@
-"""ctypes / numpy side of tests/kprobe/libkprobe.so (single launch wrappers of the suffix sorter behind C functions),
-the plain references the kernel tests compare with, and the generator of legal active lists.
+"""ctypes / numpy side of tests/kprobe/libkprobe.so (single launch wrappers of the suffix sorter and of the prefix-free parse
+behind C functions), the plain references the sorter's kernel tests compare with, the generator of legal active lists, and
+(at the end) the texts, the packer and the thin wrappers of the parse's probes, whose references are tests/pfpmodel.py.
 
 Everything in the references is integer arithmetic on numpy arrays or Python ints: there is no tolerance anywhere.
 The references import nothing from the product; tests/test_sorter_reference_host.py checks them (and the generator)
@@ -526,3 +527,327 @@ def round_bound(n, h0):
     while h0 * (1 << r) < n:
         r += 1
     return r + 1
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the prefix-free parse: how a text goes to the probe (both layouts of csrc/textref.hpp) and its thin wrappers.
+# The references of these kernels are tests/pfpmodel.py.
+# ---------------------------------------------------------------------------------------------------------------------
+def c_u64(v):
+    return ctypes.c_uint64(int(v) & 0xFFFFFFFFFFFFFFFF)
+
+
+class KpText(ctypes.Structure):
+    _fields_ = [("v", ctypes.c_void_p), ("v_len", ctypes.c_uint64), ("misalign", ctypes.c_uint32),
+                ("packed", ctypes.c_void_p), ("n_words", ctypes.c_uint64), ("excw", ctypes.c_void_p), ("n_excw", ctypes.c_uint64),
+                ("runs", ctypes.c_void_p), ("n_runs", ctypes.c_uint32), ("n", ctypes.c_uint64)]
+
+
+TX_BLOCK = 4096
+_CODE = {65: 0, 67: 1, 71: 2, 84: 3}
+
+
+def pack_text(text):
+    """The packed layout documented at the top of textref.hpp: (words, excw, runs).  words: 2-bit codes (A C G T -> 0 1 2 3),
+    text position p in bits [2 (p & 31), + 2) of word p >> 5, two words of padding; every other byte has code 0 and belongs
+    to a run (start, length, byte) -- runs maximal, sorted, disjoint; bit b of excw[b >> 6]: positions [4096 b, + 4096) hold
+    part of a run.  runs is an (n_runs, 4) uint32 array: start low, start high, length, byte (the 16-byte record)."""
+    text = u8(text); n = len(text)
+    words = [0] * ((n + 31) // 32 + 2)
+    n_blocks = (n >> 12) + 1
+    flags = [0] * ((n_blocks >> 6) + 1)
+    runs = []
+    for p in range(n):
+        b = int(text[p])
+        c = _CODE.get(b)
+        if c is None:
+            if runs and runs[-1][3] == b and runs[-1][0] + runs[-1][2] == p:
+                runs[-1][2] += 1
+            else:
+                runs.append([p, 0, 1, b])
+            flags[(p >> 12) >> 6] |= 1 << ((p >> 12) & 63)
+        else:
+            words[p >> 5] |= c << (2 * (p & 31))
+    for r in runs:
+        r[0], r[1] = r[0] & 0xFFFFFFFF, r[0] >> 32
+    return u64(words), u64(flags), np.array(runs, dtype=U32).reshape(-1, 4)
+
+
+class Text:
+    """a text for the probe.  layout "bytes": V = 0x02 . T . 0x02^32 . zeros (64 bytes of them and more), placed so that
+    (v + 1) mod 16 = misalign; layout "packed": the arrays of pack_text"""
+
+    def __init__(self, text, layout="bytes", misalign=0, pad=64):
+        self.text = u8(text); self.n = len(self.text); self.layout = layout
+        self.v = np.concatenate([np.full(1, 2, U8), self.text, np.full(32, 2, U8), np.zeros(pad, U8)])
+        self.c = KpText()
+        self.c.n = self.n
+        if layout == "bytes":
+            self.c.v = self.v.ctypes.data; self.c.v_len = len(self.v); self.c.misalign = misalign
+        else:
+            assert layout == "packed" and misalign == 0
+            self.words, self.excw, self.runs = pack_text(self.text)
+            self.c.packed = self.words.ctypes.data; self.c.n_words = len(self.words)
+            self.c.excw = self.excw.ctypes.data; self.c.n_excw = len(self.excw)
+            self.c.runs = self.runs.ctypes.data if len(self.runs) else None; self.c.n_runs = len(self.runs)
+
+    def arg(self):
+        return ctypes.byref(self.c)
+
+
+def _pos(a, wide):
+    return np.ascontiguousarray(a, dtype=U64 if wide else U32)
+
+
+def _sent_pos(n, wide):
+    return np.full(n, SENT64, U64) if wide else np.full(n, SENT32, U32)
+
+
+def trigger_blocks(n):
+    out = np.zeros(1, U32)
+    call("trigger_blocks", c_u64(n), out)
+    return int(out[0])
+
+
+def emit_tile():
+    out = np.zeros(1, U32)
+    call("emit_tile", out)
+    return int(out[0])
+
+
+def trigger_masks(tx, w, p, extra=3):
+    """(masks, block_count), both with `extra` sentinel entries behind what the wrapper may write"""
+    n = tx.n
+    masks = np.full((n + 15) // 16 + extra, 0xA5A5, np.uint16)
+    counts = np.full(max(1, ((n + 15) // 16 + 255) // 256) + extra, SENT32, U32)
+    call("trigger_masks", tx.arg(), c_u64(n), w, c_u32(p), masks, len(masks), counts, len(counts))
+    return masks, counts
+
+
+def trigger_cuts(masks, n, block_off, alloc, wide):
+    cuts = _sent_pos(alloc, wide)
+    call("trigger_cuts", np.ascontiguousarray(masks, dtype=np.uint16), c_u64(n), u32(block_off), cuts, alloc, int(wide))
+    return cuts
+
+
+def phrase_bounds(cuts, n, w, wide, extra=2):
+    cuts = _pos(cuts, wide); k = len(cuts)
+    start = _sent_pos(k + 1 + extra, wide); length = np.full(k + 1 + extra, SENT32, U32)
+    call("phrase_bounds", cuts, k, c_u64(n), w, start, length, k + 1 + extra, int(wide))
+    return start, length
+
+
+def phrase_hash(tx, start, length, wide=False, extra=2):
+    start = _pos(start, wide); m = len(start)
+    h1 = np.full(m + extra, SENT64, U64); pinfo = np.full((m + extra, 4), SENT32, U32)
+    call("phrase_hash", tx.arg(), start, u32(length), m, h1, pinfo, m + extra, int(wide))
+    return h1, pinfo
+
+
+def second_fingerprint(pinfo, extra=2):
+    pinfo = u32(pinfo).reshape(-1, 4); m = len(pinfo)
+    h2 = np.full(m + extra, SENT64, U64)
+    call("second_fingerprint", pinfo, m, h2, m + extra)
+    return h2
+
+
+def mark_distinct(order, h1s, pinfo, tx, extra=2):
+    order = u32(order); m = len(order); pinfo = u32(pinfo).reshape(-1, 4)
+    flags = np.full(m + extra, SENT32, U32); err = np.zeros(16, U32); err[2:] = SENT32
+    call("mark_distinct", order, u64(h1s), pinfo, len(pinfo), tx.arg(), m, flags, m + extra, err)
+    return flags, err
+
+
+def assign_distinct(order, scan, flags, length, d_alloc):
+    m = len(order)
+    pid = np.full(m, SENT32, U32); rep = np.full(d_alloc, SENT32, U32); dlen = np.full(d_alloc, SENT32, U32)
+    call("assign_distinct", u32(order), u32(scan), u32(flags), u32(length), m, pid, rep, dlen, d_alloc)
+    return pid, rep, dlen
+
+
+def sum_u32(x):
+    x = u32(x); out = np.full(1, SENT64, U64)
+    call("sum_u32", x, len(x), out)
+    return int(out[0])
+
+
+def copy_dict(tx, start, length, which, dstart, dict_len, pack_prev, wide=False, with_info=True, extra=8):
+    start = _pos(start, wide)
+    d = np.full(dict_len + extra, SENT8, U8)
+    info = np.full(dict_len + extra, SENT64, U64) if with_info else None
+    call("copy_dict", tx.arg(), start, u32(length), len(start), u32(which), u32(dstart), len(which), d, info, dict_len + extra,
+         dict_len, int(pack_prev), int(wide))
+    return d, info
+
+
+def entry_info(sa_d, dinfo, d, pack_prev, extra=5):
+    nd = len(sa_d)
+    esuf = np.full(nd + extra, SENT32, U32); ephr = np.full(nd + extra, SENT32, U32); ebw = np.full(nd + extra, SENT8, U8)
+    call("entry_info", u32(sa_d), u64(dinfo), u8(d), nd, int(pack_prev), esuf, ephr, ebw, nd + extra)
+    return esuf, ephr, ebw
+
+
+def dict_irreducible(d, sa_d, esuf, ebw, long_cap, long_alloc):
+    nd = len(sa_d)
+    plcp = np.full(nd, SENT32, U32); longs = np.full((long_alloc, 4), SENT32, U32); cnt = np.full(1, SENT32, U32)
+    call("dict_irreducible", u8(d), nd, u32(sa_d), u32(esuf), u8(ebw), plcp, longs, long_alloc, cnt, long_cap)
+    return plcp, longs, int(cnt[0])
+
+
+def long_lcp_lim(d, longs, plcp):
+    longs = u32(longs).reshape(-1, 4); plcp = u32(plcp).copy()
+    call("long_lcp_lim", u8(d), len(d), longs, len(longs), plcp)
+    return plcp
+
+
+def plcp_running_max(plcp, extra=3):
+    n = len(plcp)
+    a = np.concatenate([u32(plcp), np.full(extra, SENT32, U32)])
+    call("plcp_running_max", a, n, n + extra)
+    return a
+
+
+def lcp_gather(plcp, sa, extra=5):
+    n = len(sa)
+    out = np.full(n + extra, SENT32, U32)
+    call("lcp_gather", u32(plcp), len(plcp), u32(sa), n, out, n + extra)
+    return out
+
+
+def dict_lcp_clamp(lcp, esuf, extra=3):
+    nd = len(esuf)
+    a = np.concatenate([u32(lcp)[:nd], np.full(extra, SENT32, U32)])
+    call("dict_lcp_clamp", a, u32(esuf), nd, nd + extra)
+    return a
+
+
+def group_flags(esuf, lcp_d, w, extra=2):
+    nd = len(esuf)
+    g, p, v = (np.full(nd + extra, SENT32, U32) for _ in range(3)); seg = np.full(nd + extra, SENT64, U64)
+    call("group_flags", u32(esuf), u32(lcp_d), nd, w, g, p, v, seg, nd + extra)
+    return g, p, v, seg
+
+
+def phrase_ranks(esuf, ephr, pscan, alloc):
+    prank = np.full(alloc, SENT32, U32)
+    call("phrase_ranks", u32(esuf), u32(ephr), u32(pscan), len(esuf), prank, alloc)
+    return prank
+
+
+def parse_ranks(pid, prank, extra=2):
+    m = len(pid); out = np.full(m + extra, SENT32, U32)
+    call("parse_ranks", u32(pid), u32(prank), len(prank), m, out, m + extra)
+    return out
+
+
+def invert_ranks(prank, rep, dlen, extra=2):
+    d = len(prank)
+    which = np.full(d + extra, SENT32, U32); slen = np.full(d + extra, SENT32, U32)
+    call("invert_ranks", u32(prank), u32(rep), u32(dlen), d, which, slen, d + extra)
+    return which, slen
+
+
+def occ_sequence(sa_p, pid, n_distinct, extra=2):
+    m = len(sa_p)
+    keys = np.full(m + 1 + extra, SENT32, U32); vals = np.full(m + 1 + extra, SENT32, U32)
+    call("occ_sequence", u32(sa_p), u32(pid), m, c_u32(n_distinct), keys, vals, m + 1 + extra)
+    return keys, vals
+
+
+def occ_finish(mode, ids, ts, sa_p, pstart, wide, sl, pos_bits, n_start, extra=2):
+    """mode 8: (occ_start, occ u64, occ_sl); mode 12: (occ_start, occ12 (m + extra, 3), None)"""
+    m = len(sa_p)
+    occ_start = np.full(n_start, SENT32, U32)
+    occ = np.full(m + extra, SENT64, U64) if mode == 8 else np.full((m + extra, 3), SENT32, U32)
+    occ_sl = np.full(m + extra, SENT32, U32) if mode == 8 else None
+    call("occ_finish", mode, u32(ids), u32(ts), u32(sa_p), _pos(pstart, wide), int(wide), m, occ_start, n_start, occ, m + extra,
+         pos_bits, u32(sl), occ_sl)
+    return occ_start, occ, occ_sl
+
+
+def phrase_table(occ_start, plen, rep, extra=2):
+    d = len(rep); tab = np.full((d + extra, 4), SENT32, U32)
+    call("phrase_table", u32(occ_start), u32(plen), len(plen), u32(rep), d, tab, d + extra)
+    return tab
+
+
+def entry_compact(esuf, ephr, ebw, gflag, gscan, vflag, vscan, seg_min, tab, n_entries, extra=2):
+    a = n_entries + extra
+    cols = {k: np.full(a, SENT32, U32) for k in ("cnt", "first", "offm1", "gs", "hl", "slen")}
+    cols["bwt"] = np.full(a, SENT8, U8)
+    tab = u32(tab).reshape(-1, 4)
+    call("entry_compact", u32(esuf), u32(ephr), u8(ebw), u32(gflag), u32(gscan), u32(vflag), u32(vscan), u64(seg_min), tab, len(tab),
+         len(esuf), a, cols["cnt"], cols["first"], cols["offm1"], cols["bwt"], cols["gs"], cols["hl"], cols["slen"])
+    return cols
+
+
+def group_heads(sege, ce_hl, ce_slen, extra=2):
+    g = len(sege); out = np.full((g + extra, 2), SENT32, U32)
+    call("group_heads", u32(sege), u32(ce_hl), u32(ce_slen), len(ce_hl), g, out, g + extra)
+    return out
+
+
+def tile_first(segb, tiles, wide, tile_base=0, extra=2):
+    segb = _pos(segb, wide)
+    out = np.full(tiles - tile_base + 1 + extra, SENT32, U32)
+    call("tile_first", segb, len(segb), c_u64(tiles), out, len(out), int(wide), c_u64(tile_base))
+    return out
+
+
+def oversize(segb, wide, extra=2):
+    segb = _pos(segb, wide); g = len(segb) - 1
+    osize = np.full(g + extra, SENT32, U32); err = np.zeros(16, U32); err[3:] = SENT32
+    call("oversize", segb, g, osize, g + extra, err, int(wide))
+    return osize, err
+
+
+def gather_pos(src, idx, wide, extra=2):
+    src = _pos(src, wide); out = _sent_pos(len(idx) + extra, wide)
+    call("gather_pos", src, len(src), u32(idx), len(idx), out, len(out), int(wide))
+    return out
+
+
+def relative_offsets(fb_off, f0, count, wide, extra=2):
+    fb_off = _pos(fb_off, wide); rel = np.full(count + 1 + extra, SENT32, U32)
+    call("relative_offsets", fb_off, len(fb_off), f0, count, rel, len(rel), int(wide))
+    return rel
+
+
+def iota(n, extra=3):
+    out = np.full(n + extra, SENT32, U32)
+    call("iota", out, n, n + extra)
+    return out
+
+
+def gather_u64(src, idx, extra=2):
+    out = np.full(len(idx) + extra, SENT64, U64)
+    call("gather_u64", u64(src), len(src), u32(idx), len(idx), out, len(out))
+    return out
+
+
+def _rmq_alloc(m):
+    nb = (m + 63) // 64
+    return nb * (nb.bit_length() + 1) + 8
+
+
+def build_rmq(vals):
+    """(nb, levels, bmin with sentinels behind levels * nb entries)"""
+    vals = u32(vals); bmin = np.full(_rmq_alloc(len(vals)), SENT32, U32); dims = np.zeros(2, U32)
+    call("build_rmq", vals, len(vals), bmin, len(bmin), dims)
+    return int(dims[0]), int(dims[1]), bmin
+
+
+def rmq_query(vals, pairs):
+    """(rmq_min, rmq_min8) of every (a, b)"""
+    vals = u32(vals); ab = u32(pairs).reshape(-1, 2)
+    out = np.full(len(ab), SENT32, U32); out8 = np.full(len(ab), SENT32, U32)
+    call("rmq_query", vals, len(vals), ab, len(ab), out, out8)
+    return out, out8
+
+
+def parse_lcp(tx, nv, sa_p, pid, pstart, wide):
+    """ParseLcp::build: (sl, bmin, nb, levels, n_irreducible, n_long)"""
+    m = len(sa_p)
+    sl = np.full(m, SENT32, U32); bmin = np.full(_rmq_alloc(m), SENT32, U32); dims = np.zeros(4, U32)
+    call("parse_lcp", tx.arg(), c_u64(nv), u32(sa_p), u32(pid), _pos(pstart, wide), int(wide), m, sl, bmin, len(bmin), dims)
+    return sl, bmin, int(dims[0]), int(dims[1]), int(dims[2]), int(dims[3])

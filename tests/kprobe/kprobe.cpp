@@ -1,5 +1,6 @@
 // kprobe.cpp -- test infrastructure: plain C entry points around single launch wrappers of the suffix sorter
-// (mmt::k, mmt::prims, pk::pack_keys_u32, DoublingSorter::sort), for tests/kprobe.py.
+// (mmt::k, mmt::prims, pk::pack_keys_u32, DoublingSorter::sort) and of the prefix-free parse (mmt::pk rows A2-A4, the
+// dictionary's LCP steps of mmt::k, build_rmq / ParseLcp::build / rmq_min of parse_lcp.hpp), for tests/kprobe.py.
 //
 // Every kp_* function takes host arrays, uploads them, calls exactly ONE wrapper, synchronises and copies the results
 // back; arrays marked "in/out" go up as the caller filled them (sentinel patterns: what the wrapper must not touch
@@ -8,14 +9,17 @@
 // own copy of the device heap and of the switch table; nothing of the product is restated here.
 //
 // Adding a wrapper: one KP function below (upload with Dev<T>, call, down()), one ctypes line in tests/kprobe.py.
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <stdexcept>
 #include <string>
 
 #include <hip/hip_runtime.h>
 
 #include "device_utils.hpp"
 #include "kernels.hpp"
+#include "parse_lcp.hpp"
 #include "pfp_kernels.hpp"
 #include "prims.hpp"
 #include "sorter.hpp"
@@ -385,5 +389,491 @@ KP int kp_sorter_ints(const u32* parse, u32 m, int bits, int chars, u32* sa, u32
         out[0] = (u64)S.sort(m, bits * chars, (u64)chars, dsa.p(), dr.p(), temp.b, stream());
         out[1] = S.run_refined();
         dsa.down(sa); dr.down(rank);
+    });
+}
+
+// ==== the prefix-free parse (pfp_kernels.hpp rows A2-A4, the dictionary's LCP steps of kernels.hpp, parse_lcp.hpp) =============
+// Position tables go as untyped host pointers with `wide` (uint32_t or uint64_t entries), as the wrappers take them.  Before
+// a launch every index a kernel will follow is checked on the host against the sizes the caller gave: a forged input that
+// breaks a wrapper's precondition is an error message, never a stray access on the device.
+static void need(bool ok, const char* what) { if (!ok) throw std::runtime_error(std::string("kprobe precondition: ") + what); }
+static u64 pos_at(const void* a, bool wide, size_t i) { return wide ? ((const u64*)a)[i] : (u64)((const u32*)a)[i]; }
+struct DevPos {                         // a position table (count entries of 4 or 8 bytes)
+    Dev<u8> d; bool wide; size_t count;
+    DevPos(const void* h, size_t n, bool w) : d((const u8*)h, n * (w ? 8 : 4)), wide(w), count(n) {}
+    void* p() { return d.p(); }
+    void down(void* h) { d.down((u8*)h); }
+};
+
+// The text as tests/kprobe.py hands it over.  BYTES (v != null): V = Dollar . T . Dollar^32 . zeros, v_len bytes of which at
+// least 64 are zero padding; it is placed so that (v + 1) mod 16 = misalign (0: as Engine::text_ptr places it).  PACKED: the
+// arrays of textref.hpp as the packer of tests/kprobe.py laid them out, uploaded as given.
+struct KpText {
+    const u8* v; u64 v_len; u32 misalign;
+    const u64* packed; u64 n_words; const u64* excw; u64 n_excw; const ExcRun* runs; u32 n_runs;
+    u64 n;
+};
+struct DevText {
+    DevBuf<u8> bytes;
+    Dev<u64> pk, ex;
+    Dev<ExcRun> rn;
+    TextRef T;
+    u64 readable;                       // V indices below this may be read (bytes: v_len; packed: any -- tx_byte gives zeros)
+    explicit DevText(const KpText* t)
+        : pk(t->v ? nullptr : t->packed, t->v ? 0 : t->n_words), ex(t->v ? nullptr : t->excw, t->v ? 0 : t->n_excw),
+          rn(t->v ? nullptr : t->runs, t->v ? 0 : t->n_runs) {
+        T.n = t->n;
+        if (t->v) {
+            need(t->misalign < 16, "misalign 0..15");
+            need(t->v_len >= t->n + 33 + 64, "V is Dollar, the text, 32 Dollars and at least 64 zero bytes");
+            const size_t total = (size_t)t->v_len + 32 + 128;
+            bytes.ensure(total);
+            MMT_HIP(hipMemsetAsync(bytes.get(), 0, total, stream()));
+            const uintptr_t base = reinterpret_cast<uintptr_t>(bytes.get());
+            const size_t k = 16 + ((t->misalign + 32 - 1 - (base & 15)) & 15);          // (base + k + 1) mod 16 = misalign
+            MMT_HIP(hipMemcpyAsync(bytes.get() + k, t->v, t->v_len, hipMemcpyHostToDevice, stream()));
+            sync();
+            T.v = bytes.get() + k;
+            readable = t->v_len;
+        } else {
+            need(t->n_words >= (t->n + 31) / 32 + 2, "packed text: two words of padding");
+            need(t->n_excw >= ((t->n >> TX_BLOCK_SHIFT) >> 6) + 1, "packed text: one flag per 4096 positions");
+            T.packed = pk.p(); T.excw = ex.p(); T.runs = rn.p(); T.n_runs = t->n_runs;
+            readable = ~0ull;
+        }
+    }
+};
+
+// ---- A2: triggers, cuts, phrases -----------------------------------------------------------------------------------
+KP int kp_trigger_blocks(u64 n, u32* out) { return guarded([&] { *out = pk::trigger_blocks(n); }); }
+KP int kp_emit_tile(u32* out) { return guarded([&] { *out = pk::emit_tile(); }); }
+// masks (masks_len entries), block_count (count_len entries): in/out
+KP int kp_trigger_masks(const KpText* tx, u64 n, u32 w, u32 p, uint16_t* masks, u32 masks_len, u32* block_count, u32 count_len) {
+    return guarded([&] {
+        need(n >= 1 && n == tx->n && w >= 1 && w <= 32 && p >= 1, "n = text length >= 1, 1 <= w <= 32, p >= 1");
+        need(masks_len >= (n + 15) / 16 && count_len >= pk::trigger_blocks(n), "masks / block_count too short");
+        DevText t(tx);
+        Dev<uint16_t> m(masks, masks_len);
+        Dev<u32> c(block_count, count_len);
+        pk::trigger_masks(t.T, n, w, p, m.p(), c.p(), stream());
+        m.down(masks); c.down(block_count);
+    });
+}
+// cuts (cuts_len entries of 4 / 8 bytes): in/out
+KP int kp_trigger_cuts(const uint16_t* masks, u64 n, const u32* block_off, void* cuts, u32 cuts_len, int wide) {
+    return guarded([&] {
+        const u64 threads = (n + 15) / 16;
+        const u32 blocks = pk::trigger_blocks(n);
+        for (u32 b = 0; b < blocks; b++) {
+            u64 c = 0;
+            for (u64 t = (u64)b * 256; t < std::min<u64>(threads, (u64)(b + 1) * 256); t++) c += __builtin_popcount(masks[t]);
+            need((u64)block_off[b] + c <= cuts_len, "block_off + the block's triggers beyond the cut list");
+        }
+        Dev<uint16_t> m(masks, threads);
+        Dev<u32> o(block_off, blocks);
+        DevPos c(cuts, cuts_len, wide != 0);
+        pk::trigger_cuts(m.p(), n, o.p(), c.p(), wide != 0, stream());
+        c.down(cuts);
+    });
+}
+// start, len (alloc entries): in/out
+KP int kp_phrase_bounds(const void* cuts, u32 n_cuts, u64 n, u32 w, void* start, u32* len, u32 alloc, int wide) {
+    return guarded([&] {
+        need(alloc >= (u64)n_cuts + 1, "start / len hold n_cuts + 1 entries");
+        DevPos c(cuts, n_cuts, wide != 0), s(start, alloc, wide != 0);
+        Dev<u32> l(len, alloc);
+        pk::phrase_bounds(c.p(), n_cuts, n, w, s.p(), l.p(), wide != 0, stream());
+        s.down(start); l.down(len);
+    });
+}
+
+// ---- A2: fingerprints and distinct phrases ---------------------------------------------------------------------------
+// h1 (alloc entries), pinfo (4 * alloc words): in/out
+KP int kp_phrase_hash(const KpText* tx, const void* start, const u32* len, u32 m, u64* h1, u32* pinfo, u32 alloc, int wide) {
+    return guarded([&] {
+        need(alloc >= m, "h1 / pinfo hold m entries");
+        DevText t(tx);
+        for (u32 k = 0; k < m; k++) need(pos_at(start, wide != 0, k) + len[k] <= t.readable, "a phrase beyond V");
+        DevPos s(start, m, wide != 0);
+        Dev<u32> l(len, m), pi(pinfo, 4 * (size_t)alloc);
+        Dev<u64> h(h1, alloc);
+        pk::phrase_hash(t.T, s.p(), l.p(), m, h.p(), pi.p(), wide != 0, stream());
+        h.down(h1); pi.down(pinfo);
+    });
+}
+KP int kp_second_fingerprint(const u32* pinfo, u32 m, u64* h2, u32 alloc) {                    // h2: in/out
+    return guarded([&] {
+        need(alloc >= m, "h2 holds m entries");
+        Dev<u32> pi(pinfo, 4 * (size_t)m);
+        Dev<u64> h(h2, alloc);
+        pk::second_fingerprint(pi.p(), m, h.p(), stream());
+        h.down(h2);
+    });
+}
+// pinfo: n_rec records; flags (alloc entries), err (16 words): in/out
+KP int kp_mark_distinct(const u32* order, const u64* h1s, const u32* pinfo, u32 n_rec, const KpText* tx, u32 m, u32* flags,
+                        u32 alloc, u32* err) {
+    return guarded([&] {
+        need(alloc >= m, "flags holds m entries");
+        DevText t(tx);
+        for (u32 k = 0; k < m; k++) {
+            need(order[k] < n_rec, "order beyond the records");
+            const u32* r = pinfo + 4 * (size_t)order[k];
+            need((((u64)(r[1] >> 24) << 32) | r[2]) + r[3] <= t.readable, "a record's phrase beyond V");
+        }
+        Dev<u32> o(order, m), pi(pinfo, 4 * (size_t)n_rec), f(flags, alloc), e(err, 16);
+        Dev<u64> h(h1s, m);
+        pk::mark_distinct(o.p(), h.p(), pi.p(), t.T, m, f.p(), e.p(), stream());
+        f.down(flags); e.down(err);
+    });
+}
+// pid (m entries), rep, dlen (d_alloc entries): in/out
+KP int kp_assign_distinct(const u32* order, const u32* scan, const u32* flags, const u32* len, u32 m, u32* pid, u32* rep,
+                          u32* dlen, u32 d_alloc) {
+    return guarded([&] {
+        for (u32 k = 0; k < m; k++) need(order[k] < m && scan[k] >= 1 && scan[k] <= d_alloc, "order / scan out of range");
+        Dev<u32> o(order, m), sc(scan, m), f(flags, m), l(len, m), p(pid, m), r(rep, d_alloc), d(dlen, d_alloc);
+        pk::assign_distinct(o.p(), sc.p(), f.p(), l.p(), m, p.p(), r.p(), d.p(), stream());
+        p.down(pid); r.down(rep); d.down(dlen);
+    });
+}
+KP int kp_sum_u32(const u32* x, u32 n, u64* out) {                                           // out: in/out, one entry
+    return guarded([&] {
+        Dev<u32> a(x, n);
+        Dev<u64> o(out, 1);
+        pk::sum_u32(a.p(), n, o.p(), stream());
+        o.down(out);
+    });
+}
+
+// ---- A2/A3: dictionary ------------------------------------------------------------------------------------------------
+// start, len: n_phrases entries; dict (dict_alloc bytes), dinfo (dict_alloc entries, or null): in/out
+KP int kp_copy_dict(const KpText* tx, const void* start, const u32* len, u32 n_phrases, const u32* which, const u32* dstart,
+                    u32 n_phr, u8* dict, u64* dinfo, u32 dict_alloc, u32 dict_len, int pack_prev, int wide) {
+    return guarded([&] {
+        need(dict_len >= 1 && dict_len <= dict_alloc, "dict_len within the dictionary");
+        DevText t(tx);
+        for (u32 k = 0; k < n_phr; k++) {
+            need(which[k] < n_phrases, "which beyond the phrases");
+            need(len[which[k]] >= 1 && pos_at(start, wide != 0, which[k]) + len[which[k]] <= t.readable, "a phrase beyond V");
+        }
+        DevPos s(start, n_phrases, wide != 0);
+        Dev<u32> l(len, n_phrases), wh(which, n_phr), ds(dstart, n_phr);
+        Dev<u8> d(dict, dict_alloc);
+        Dev<u64> di(dinfo, dinfo ? dict_alloc : 0);
+        pk::copy_dict(t.T, s.p(), l.p(), wh.p(), ds.p(), n_phr, d.p(), dinfo ? di.p() : nullptr, dict_len, pack_prev != 0,
+                      wide != 0, stream());
+        d.down(dict); di.down(dinfo);
+    });
+}
+// a dictionary on the device: nd bytes and the 64 zero bytes the product keeps behind them
+struct DevDict {
+    DevBuf<u8> b;
+    DevDict(const u8* h, u32 nd) {
+        b.ensure((size_t)nd + 128);
+        MMT_HIP(hipMemsetAsync(b.get(), 0, (size_t)nd + 128, stream()));
+        if (nd) MMT_HIP(hipMemcpyAsync(b.get(), h, nd, hipMemcpyHostToDevice, stream()));
+        sync();
+    }
+    u8* p() { return b.get(); }
+};
+// esuf, ephr, ebw (alloc entries): in/out
+KP int kp_entry_info(const u32* sa_d, const u64* dinfo, const u8* dict, u32 nd, int pack_prev, u32* esuf, u32* ephr, u8* ebw,
+                     u32 alloc) {
+    return guarded([&] {
+        need(alloc >= nd, "the columns hold nd entries");
+        for (u32 r = 0; r < nd; r++) need(sa_d[r] < nd, "sa_d beyond the dictionary");
+        Dev<u32> sa(sa_d, nd), es(esuf, alloc), ep(ephr, alloc);
+        Dev<u64> di(dinfo, nd);
+        Dev<u8> eb(ebw, alloc);
+        DevDict d(dict, nd);
+        pk::entry_info(sa.p(), di.p(), d.p(), nd, pack_prev != 0, es.p(), ep.p(), eb.p(), stream());
+        es.down(esuf); ep.down(ephr); eb.down(ebw);
+    });
+}
+static void check_dict_entries(const u32* sa_d, const u32* esuf, u32 nd) {
+    for (u32 r = 0; r < nd; r++) need(sa_d[r] < nd && (u64)sa_d[r] + (esuf[r] & 0x7fffffffu) <= nd, "a phrase suffix beyond the dictionary");
+}
+// plcp (nd entries): out; longs (4 * long_alloc words), long_count: in/out
+KP int kp_dict_irreducible(const u8* dict, u32 nd, const u32* sa_d, const u32* esuf, const u8* ebw, u32* plcp, u32* longs,
+                           u32 long_alloc, u32* long_count, u32 long_cap) {
+    return guarded([&] {
+        need(long_cap <= long_alloc, "long_cap beyond the list");
+        check_dict_entries(sa_d, esuf, nd);
+        DevDict d(dict, nd);
+        Dev<u32> sa(sa_d, nd), es(esuf, nd), pl(nullptr, nd), lg(longs, 4 * (size_t)long_alloc), lc(long_count, 1);
+        Dev<u8> eb(ebw, nd);
+        pk::dict_irreducible(d.p(), nd, sa.p(), es.p(), eb.p(), pl.p(), lg.p(), lc.p(), long_cap, stream());
+        pl.down(plcp); lg.down(longs); lc.down(long_count);
+    });
+}
+// longs: count records (p, q, h, lim); plcp (nd entries): in/out
+KP int kp_long_lcp_lim(const u8* dict, u32 nd, const u32* longs, u32 count, u32* plcp) {
+    return guarded([&] {
+        for (u32 i = 0; i < count; i++) {
+            const u32* r = longs + 4 * (size_t)i;
+            need(r[0] < nd && r[1] < nd && (u64)std::max(r[0], r[1]) + r[3] <= nd && r[2] <= r[3], "a record beyond the dictionary");
+        }
+        DevDict d(dict, nd);
+        Dev<u32> lg(longs, 4 * (size_t)count), pl(plcp, nd), huge(nullptr, (size_t)count + 1), hc(nullptr, 1);
+        k::long_lcp_lim(d.p(), nd, lg.p(), count, pl.p(), huge.p(), hc.p(), stream());
+        pl.down(plcp);
+    });
+}
+KP int kp_plcp_running_max(u32* plcp, u32 n, u32 alloc) {                                    // plcp (alloc entries): in/out
+    return guarded([&] {
+        need(alloc >= n, "plcp holds n entries");
+        Dev<u32> pl(plcp, alloc);
+        Dev<u8> scratch(nullptr, k::plcp_running_max_scratch(n));
+        k::plcp_running_max(pl.p(), n, scratch.p(), stream());
+        pl.down(plcp);
+    });
+}
+KP int kp_lcp_gather(const u32* plcp, u32 n, const u32* sa, u32 count, u32* lcp, u32 alloc) {   // lcp (alloc entries): in/out
+    return guarded([&] {
+        need(alloc >= count, "lcp holds count entries");
+        for (u32 j = 0; j < count; j++) need(sa[j] < n, "sa beyond plcp");
+        Dev<u32> pl(plcp, n), a(sa, count), o(lcp, alloc);
+        SaCol col; col.lo = a.p(); col.hi = nullptr;
+        k::lcp_gather(pl.p(), col, 0, count, o.p(), stream());
+        o.down(lcp);
+    });
+}
+KP int kp_dict_lcp_clamp(u32* lcp, const u32* esuf, u32 nd, u32 alloc) {                     // lcp (alloc entries): in/out
+    return guarded([&] {
+        need(alloc >= nd, "lcp holds nd entries");
+        Dev<u32> l(lcp, alloc), es(esuf, nd);
+        pk::dict_lcp_clamp(l.p(), es.p(), nd, stream());
+        l.down(lcp);
+    });
+}
+
+// ---- A3: groups, ranks ------------------------------------------------------------------------------------------------
+// gflag, pflag, vflag, seg (alloc entries): in/out
+KP int kp_group_flags(const u32* esuf, const u32* lcp_d, u32 nd, u32 w, u32* gflag, u32* pflag, u32* vflag, u64* seg, u32 alloc) {
+    return guarded([&] {
+        need(alloc >= nd, "the columns hold nd entries");
+        Dev<u32> es(esuf, nd), l(lcp_d, nd), g(gflag, alloc), p(pflag, alloc), v(vflag, alloc);
+        Dev<u64> sg(seg, alloc);
+        pk::group_flags(es.p(), l.p(), nd, w, g.p(), p.p(), v.p(), sg.p(), stream());
+        g.down(gflag); p.down(pflag); v.down(vflag); sg.down(seg);
+    });
+}
+KP int kp_phrase_ranks(const u32* esuf, const u32* ephr, const u32* pscan, u32 nd, u32* prank, u32 alloc) {     // prank: in/out
+    return guarded([&] {
+        for (u32 r = 0; r < nd; r++) need(!(esuf[r] >> 31) || ephr[r] < alloc, "ephr beyond prank");
+        Dev<u32> es(esuf, nd), ep(ephr, nd), ps(pscan, nd), pr(prank, alloc);
+        pk::phrase_ranks(es.p(), ep.p(), ps.p(), nd, pr.p(), stream());
+        pr.down(prank);
+    });
+}
+KP int kp_parse_ranks(const u32* pid, const u32* prank, u32 n_distinct, u32 m, u32* parse, u32 alloc) {          // parse: in/out
+    return guarded([&] {
+        need(alloc >= m, "parse holds m entries");
+        for (u32 q = 0; q < m; q++) need(pid[q] < n_distinct, "pid beyond prank");
+        Dev<u32> pi(pid, m), pr(prank, n_distinct), o(parse, alloc);
+        pk::parse_ranks(pi.p(), pr.p(), m, o.p(), stream());
+        o.down(parse);
+    });
+}
+KP int kp_invert_ranks(const u32* prank, const u32* rep, const u32* dlen, u32 n_distinct, u32* which, u32* slen, u32 alloc) {
+    return guarded([&] {
+        for (u32 d = 0; d < n_distinct; d++) need(prank[d] >= 1 && prank[d] <= alloc, "prank is 1 .. alloc");
+        Dev<u32> pr(prank, n_distinct), r(rep, n_distinct), dl(dlen, n_distinct), wh(which, alloc), sl(slen, alloc);
+        pk::invert_ranks(pr.p(), r.p(), dl.p(), n_distinct, wh.p(), sl.p(), stream());
+        wh.down(which); sl.down(slen);
+    });
+}
+
+// ---- A4: inverted lists and emitter tables ----------------------------------------------------------------------------
+KP int kp_occ_sequence(const u32* sa_p, const u32* pid, u32 m, u32 D, u32* keys, u32* vals, u32 alloc) {         // keys, vals: in/out
+    return guarded([&] {
+        need(m >= 1 && alloc >= (u64)m + 1, "keys / vals hold m + 1 entries");
+        for (u32 r = 0; r < m; r++) need(sa_p[r] < m, "sa_p beyond the parse");
+        Dev<u32> sa(sa_p, m), pi(pid, m), kk(keys, alloc), vv(vals, alloc);
+        pk::occ_sequence(sa.p(), pi.p(), m, D, kk.p(), vv.p(), stream());
+        kk.down(keys); vv.down(vals);
+    });
+}
+static void check_occ(const u32* ids, const u32* ts, const u32* sa_p, u32 m, u32 start_alloc) {
+    need(m >= 1, "m >= 1");
+    for (u32 k = 0; k <= m; k++) need(ids[k] < start_alloc, "ids beyond occ_start");
+    for (u32 k = 0; k < m; k++) need(ts[k] <= m && (ts[k] == 0 || (sa_p[ts[k] - 1] >= 1 && sa_p[ts[k] - 1] <= m)), "ts / sa_p out of range (the parse's first suffix belongs to the dummy, entry m)");
+}
+// mode 8: occ_finish (occ: m records of 8 bytes, occ_sl); mode 12: occ_finish12 (occ: m records of 12 bytes).
+// occ_start (start_alloc), occ (occ_alloc records), occ_sl (occ_alloc): in/out
+KP int kp_occ_finish(int mode, const u32* ids, const u32* ts, const u32* sa_p, const void* pstart, int wide, u32 m, u32* occ_start,
+                     u32 start_alloc, void* occ, u32 occ_alloc, u32 pos_bits, const u32* sl, u32* occ_sl) {
+    return guarded([&] {
+        need(mode == 8 || mode == 12, "mode 8 or 12");
+        need(occ_alloc >= m && (mode == 12 || pos_bits < 64), "occ holds m records");
+        check_occ(ids, ts, sa_p, m, start_alloc);
+        Dev<u32> i(ids, (size_t)m + 1), t(ts, (size_t)m + 1), sa(sa_p, m), os(occ_start, start_alloc), s(sl, m),
+            osl(occ_sl, mode == 8 ? occ_alloc : 0);
+        DevPos ps(pstart, m, wide != 0);
+        Dev<u8> o((const u8*)occ, (size_t)occ_alloc * mode);
+        if (mode == 8)
+            pk::occ_finish(i.p(), t.p(), sa.p(), ps.p(), m, os.p(), (u64*)o.p(), pos_bits, s.p(), osl.p(), wide != 0, stream());
+        else
+            pk::occ_finish12(i.p(), t.p(), sa.p(), ps.p(), wide != 0, m, os.p(), (u32*)o.p(), s.p(), stream());
+        os.down(occ_start); o.down((u8*)occ); osl.down(occ_sl);
+    });
+}
+KP int kp_phrase_table(const u32* occ_start, const u32* plen, u32 n_plen, const u32* rep, u32 D, u32* tab, u32 alloc) {   // tab (4 * alloc words): in/out
+    return guarded([&] {
+        need(alloc >= D, "tab holds n_distinct records");
+        for (u32 d = 0; d < D; d++) need(rep[d] < n_plen, "rep beyond plen");
+        Dev<u32> os(occ_start, (size_t)D + 1), pl(plen, n_plen), r(rep, D), tb(tab, 4 * (size_t)alloc);
+        pk::phrase_table(os.p(), pl.p(), r.p(), D, tb.p(), stream());
+        tb.down(tab);
+    });
+}
+// the compact columns (e_alloc entries each): in/out
+KP int kp_entry_compact(const u32* esuf, const u32* ephr, const u8* ebw, const u32* gflag, const u32* gscan, const u32* vflag,
+                        const u32* vscan, const u64* segmin, const u32* tab, u32 D, u32 nd, u32 e_alloc, u32* ce_cnt,
+                        u32* ce_first, u32* ce_offm1, u8* ce_bwt, u32* ce_gs, u32* ce_hl, u32* ce_slen) {
+    return guarded([&] {
+        for (u32 r = 0; r < nd; r++) need(!vflag[r] || (vscan[r] < e_alloc && ephr[r] < D), "vscan / ephr out of range");
+        Dev<u32> es(esuf, nd), ep(ephr, nd), gf(gflag, nd), gs(gscan, nd), vf(vflag, nd), vs(vscan, nd), tb(tab, 4 * (size_t)D),
+            c0(ce_cnt, e_alloc), c1(ce_first, e_alloc), c2(ce_offm1, e_alloc), c4(ce_gs, e_alloc), c5(ce_hl, e_alloc),
+            c6(ce_slen, e_alloc);
+        Dev<u8> eb(ebw, nd), c3(ce_bwt, e_alloc);
+        Dev<u64> sm(segmin, nd);
+        pk::entry_compact(es.p(), ep.p(), eb.p(), gf.p(), gs.p(), vf.p(), vs.p(), sm.p(), tb.p(), nd, c0.p(), c1.p(), c2.p(),
+                          c3.p(), c4.p(), c5.p(), c6.p(), stream());
+        c0.down(ce_cnt); c1.down(ce_first); c2.down(ce_offm1); c3.down(ce_bwt); c4.down(ce_gs); c5.down(ce_hl); c6.down(ce_slen);
+    });
+}
+KP int kp_group_heads(const u32* sege, const u32* ce_hl, const u32* ce_slen, u32 n_entries, u32 n_groups, u32* ghead, u32 alloc) {
+    return guarded([&] {
+        need(alloc >= n_groups, "ghead holds n_groups pairs");
+        for (u32 g = 0; g < n_groups; g++) need(sege[g] < n_entries && (g == 0 || sege[g] >= 1), "sege out of range");
+        Dev<u32> sg(sege, n_groups), hl(ce_hl, n_entries), sl(ce_slen, n_entries), gh(ghead, 2 * (size_t)alloc);
+        pk::group_heads(sg.p(), hl.p(), sl.p(), n_groups, gh.p(), stream());
+        gh.down(ghead);
+    });
+}
+// out (alloc entries): in/out; segb: n_groups entries
+KP int kp_tile_first(const void* segb, u32 n_groups, u64 tiles, u32* out, u32 alloc, int wide, u64 tile_base) {
+    return guarded([&] {
+        const u64 tile = pk::emit_tile();
+        need(tiles >= tile_base && tiles - tile_base + 1 <= alloc, "out holds tiles - tile_base + 1 entries");
+        for (u32 g = 0; g < n_groups; g++) {
+            need(pos_at(segb, wide != 0, g) / tile + 1 >= tile_base, "a group before the table's first tile");
+            need(g == 0 || pos_at(segb, wide != 0, g) >= pos_at(segb, wide != 0, g - 1), "segb ascends");
+        }
+        DevPos sb(segb, n_groups, wide != 0);
+        Dev<u32> o(out, alloc);
+        pk::tile_first(sb.p(), n_groups, tiles, o.p(), wide != 0, stream(), tile_base);
+        o.down(out);
+    });
+}
+// segb: n_groups + 1 entries; osize (alloc entries), err (16 words): in/out
+KP int kp_oversize(const void* segb, u32 n_groups, u32* osize, u32 alloc, u32* err, int wide) {
+    return guarded([&] {
+        need(alloc >= n_groups, "osize holds n_groups entries");
+        DevPos sb(segb, (size_t)n_groups + 1, wide != 0);
+        Dev<u32> o(osize, alloc), e(err, 16);
+        pk::oversize(sb.p(), n_groups, o.p(), e.p(), wide != 0, stream());
+        o.down(osize); e.down(err);
+    });
+}
+KP int kp_gather_pos(const void* src, u32 n_src, const u32* idx, u32 n, void* out, u32 alloc, int wide) {        // out: in/out
+    return guarded([&] {
+        need(alloc >= n, "out holds n entries");
+        for (u32 i = 0; i < n; i++) need(idx[i] < n_src, "idx beyond src");
+        DevPos s(src, n_src, wide != 0), o(out, alloc, wide != 0);
+        Dev<u32> ix(idx, n);
+        pk::gather_pos(s.p(), ix.p(), n, o.p(), wide != 0, stream());
+        o.down(out);
+    });
+}
+KP int kp_relative_offsets(const void* fb_off, u32 n_off, u32 f0, u32 count, u32* rel, u32 alloc, int wide) {    // rel: in/out
+    return guarded([&] {
+        need((u64)f0 + count < n_off && alloc >= (u64)count + 1, "fb_off[f0 .. f0 + count] and rel[0 .. count]");
+        DevPos f(fb_off, n_off, wide != 0);
+        Dev<u32> r(rel, alloc);
+        pk::relative_offsets(f.p(), f0, count, r.p(), wide != 0, stream());
+        r.down(rel);
+    });
+}
+KP int kp_iota(u32* out, u32 n, u32 alloc) {                                                 // out: in/out
+    return guarded([&] {
+        need(alloc >= n, "out holds n entries");
+        Dev<u32> o(out, alloc);
+        pk::iota(o.p(), n, stream());
+        o.down(out);
+    });
+}
+KP int kp_gather_u64(const u64* src, u32 n_src, const u32* idx, u32 n, u64* out, u32 alloc) {                    // out: in/out
+    return guarded([&] {
+        need(alloc >= n, "out holds n entries");
+        for (u32 i = 0; i < n; i++) need(idx[i] < n_src, "idx beyond src");
+        Dev<u64> s(src, n_src), o(out, alloc);
+        Dev<u32> ix(idx, n);
+        pk::gather_u64(s.p(), ix.p(), n, o.p(), stream());
+        o.down(out);
+    });
+}
+
+// ---- parse_lcp.hpp ----------------------------------------------------------------------------------------------------
+// bmin (alloc entries): receives levels * nb entries; dims = (nb, levels)
+KP int kp_build_rmq(const u32* vals, u32 m, u32* bmin, u32 alloc, u32* dims) {
+    return guarded([&] {
+        need(m >= 1, "m >= 1");
+        Dev<u32> v(vals, m);
+        DevBuf<u32> b;
+        u32 nb = 0, levels = 0;
+        build_rmq(v.p(), m, b, nb, levels, stream());
+        sync();
+        need((u64)nb * levels <= alloc, "bmin holds levels * nb entries");
+        MMT_HIP(hipMemcpyAsync(bmin, b.get(), (size_t)nb * levels * 4, hipMemcpyDeviceToHost, stream()));
+        dims[0] = nb; dims[1] = levels;
+    });
+}
+// The one kernel of the probe: rmq_min and rmq_min8 are __device__ inlines without a host wrapper; it only calls them.
+__global__ void k_probe_rmq(RmqView R, const u32* __restrict__ ab, u32 n_pairs, u32* __restrict__ out, u32* __restrict__ out8) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pairs) return;
+    out[i] = rmq_min(R, ab[2 * i], ab[2 * i + 1]);
+    out8[i] = rmq_min8(R, ab[2 * i], ab[2 * i + 1]);
+}
+// ab: n_pairs pairs (a, b), a <= b < m; the view is the one build_rmq makes of vals inside this call
+KP int kp_rmq_query(const u32* vals, u32 m, const u32* ab, u32 n_pairs, u32* out, u32* out8) {
+    return guarded([&] {
+        need(m >= 1, "m >= 1");
+        for (u32 i = 0; i < n_pairs; i++) need(ab[2 * i] <= ab[2 * i + 1] && ab[2 * i + 1] < m, "a <= b < m");
+        Dev<u32> v(vals, m), q(ab, 2 * (size_t)n_pairs), o(nullptr, n_pairs), o8(nullptr, n_pairs);
+        DevBuf<u32> b;
+        RmqView R;
+        R.sl = v.p(); R.m = m;
+        u32 levels = 0;
+        build_rmq(v.p(), m, b, R.nb, levels, stream());
+        R.bmin = b.get();
+        if (n_pairs) {
+            hipLaunchKernelGGL(k_probe_rmq, dim3((n_pairs + 255) / 256), dim3(256), 0, stream(), R, q.p(), n_pairs, o.p(), o8.p());
+            MMT_HIP(hipGetLastError());
+        }
+        o.down(out); o8.down(out8);
+    });
+}
+// sl (m entries), bmin (alloc entries; levels * nb come back); dims = (nb, levels, n_irreducible, n_long)
+KP int kp_parse_lcp(const KpText* tx, u64 nv, const u32* sa_p, const u32* pid, const void* pstart, int wide, u32 m, u32* sl,
+                    u32* bmin, u32 alloc, u32* dims) {
+    return guarded([&] {
+        need(m >= 1, "m >= 1");
+        DevText t(tx);
+        need(nv <= t.readable && nv >= 1, "nv within V");
+        for (u32 r = 0; r < m; r++) need(sa_p[r] < m && pos_at(pstart, wide != 0, r) < nv, "sa_p / pstart out of range");
+        Dev<u32> sa(sa_p, m), pi(pid, m);
+        DevPos ps(pstart, m, wide != 0);
+        Dev<u8> temp(nullptr, 0);
+        ParseLcp L;
+        L.build(t.T, nv, sa.p(), pi.p(), ps.p(), wide != 0, m, temp.b, stream());
+        sync();
+        need((u64)L.nb * L.levels <= alloc, "bmin holds levels * nb entries");
+        MMT_HIP(hipMemcpyAsync(sl, L.sl.get(), (size_t)m * 4, hipMemcpyDeviceToHost, stream()));
+        MMT_HIP(hipMemcpyAsync(bmin, L.bmin.get(), (size_t)L.nb * L.levels * 4, hipMemcpyDeviceToHost, stream()));
+        dims[0] = L.nb; dims[1] = L.levels; dims[2] = L.n_irreducible; dims[3] = L.n_long;
     });
 }
