@@ -354,6 +354,32 @@ MMT_API int mmt_merged_inversion_calls_device(const mmt_merged* m, const int64_t
  * run passes; [3] blocks, [4] columns that needed a sort, [5] columns skipped as ascending, [6] runs found before the strand
  * and length filters, [7] calls.                                                                                        */
 MMT_API int mmt_merged_inversion_stats(const mmt_merged* m, double out[8]);
+/* ---- coverage (`mumemto coverage`: mumemto/mum_coverage.py) -------------------------------------------------------------
+ * Callers detect these entry points by their symbols; mmt_abi_version() did not change for them.
+ * What share of sequence c do the multi-MUMs of the table cover?  A row takes part in column c when its start there is not -1
+ * and its length is at least min_length; its interval is [start, min(start + length, seq_lengths[c])): a row that starts at or
+ * beyond the end of the sequence contributes nothing, one that runs over the end contributes up to it (the reference's slice
+ * assignment into a bitmap of seq_lengths[c] bools).  covered[c] is the size of the union of those intervals; a run is a
+ * maximal stretch of covered positions, half-open [begin, end), and intervals that touch belong to one run.  Strands play no
+ * part.  Fewer than 2^32 rows, starts below 2^62.
+ *
+ * mmt_merged_coverage reads the table and changes nothing of it: rows, blocks and inversion calls of m stay as they are, and
+ * partial rows are legal.  seq_lengths: n_docs host entries; seq_idx >= 0: that column, seq_idx == -1: every column (what the
+ * reference needs one invocation and one pass over the file each for); covered (may be null) receives n_docs host entries,
+ * 0 for a column not asked for.  It refuses, rc 3 and a message: a seq_idx outside [-1, n_docs), a null seq_lengths, a needed
+ * seq_lengths[c] <= 0 (the reference divides by it).  A table without rows is legal: all 0, no runs.  Calling it again
+ * replaces the results; mmt_merged_collinear and mmt_merged_sort_like_direct, which replace the table, drop them.          */
+MMT_API int mmt_merged_coverage(mmt_engine* e, mmt_merged* m, const int64_t* seq_lengths, int64_t seq_idx,
+                                int64_t min_length, uint64_t* covered);
+/* run_begin receives n_docs + 1 host entries: the runs of column c are [run_begin[c], run_begin[c + 1]), none for a column not
+ * asked for; runs receives 2 x run_begin[n_docs] host entries, begin and end of every run, ascending within a column.  runs
+ * may be null, to ask for the sizes first.                                                                              */
+MMT_API int mmt_merged_coverage_runs(const mmt_merged* m, uint64_t* run_begin, int64_t* runs);
+/* the same two arrays in HBM; owned by m                                                                               */
+MMT_API int mmt_merged_coverage_runs_device(const mmt_merged* m, const uint64_t** run_begin, const int64_t** runs);
+/* Of the last mmt_merged_coverage on m: out[0..3] HIP-event milliseconds of the extraction, column sorts, running maximum +
+ * sum, runs; [4] columns that needed a sort, [5] columns found ascending, [6] column batches, [7] runs in all.           */
+MMT_API int mmt_merged_coverage_stats(const mmt_merged* m, double out[8]);
 /* Re-order merged rows into the order of a direct run (lexicographic by match
  * string) using the anchor suffix ranks of the engine's last run, whose
  * document 0 must be the anchor.                              */

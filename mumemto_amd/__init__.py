@@ -18,6 +18,7 @@ from .binding import (  # noqa: F401
     find_inversions,
     library_path,
     load_library,
+    mum_coverage,
     mumemto_mem,
     mumemto_mum,
 )

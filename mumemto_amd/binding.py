@@ -84,6 +84,7 @@ GPU_ABI_SYMBOLS = [
     "mmt_engine_run_supplied", "mmt_merged_from_rows_device", "mmt_merged_collinear", "mmt_merged_blocks",
     "mmt_merged_blocks_device", "mmt_merged_collinear_stats", "mmt_merged_set_blocks", "mmt_merged_inversions",
     "mmt_merged_inversion_calls", "mmt_merged_inversion_calls_device", "mmt_merged_inversion_stats",
+    "mmt_merged_coverage", "mmt_merged_coverage_runs", "mmt_merged_coverage_runs_device", "mmt_merged_coverage_stats",
 ]
 
 
@@ -195,6 +196,10 @@ def load_library():
     L.mmt_merged_inversion_calls.argtypes = [C.c_void_p, C.c_void_p]
     L.mmt_merged_inversion_calls_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.mmt_merged_inversion_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    L.mmt_merged_coverage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+    L.mmt_merged_coverage_runs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mmt_merged_coverage_runs_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.mmt_merged_coverage_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.mmt_comm_unique_id.argtypes = [C.c_void_p]
     L.mmt_comm_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
     L.mmt_comm_destroy.argtypes = [C.c_void_p]
@@ -776,7 +781,8 @@ Engine.rows_in_direct_order = _engine_rows_in_direct_order
 
 class Merged:
     """A row table in the HBM of an engine's GPU (mmt_merged of mumemto_gpu.h): the result of a fold, or rows handed over
-    with Merged.from_rows / Merged.from_device.  collinear() computes the collinear blocks of its rows on the device."""
+    with Merged.from_rows / Merged.from_device.  collinear() computes the collinear blocks of its rows on the device,
+    inversions() the inversion calls over them, coverage() the share of every sequence its rows cover."""
 
     def __init__(self, engine, handle):
         self.engine, self.L, self.h = engine, engine.L, handle
@@ -919,6 +925,44 @@ class Merged:
         d.update(n_blocks=int(st[3]), cols_sorted=int(st[4]), cols_ascending=int(st[5]), runs=int(st[6]), calls=int(st[7]))
         return d
 
+    def coverage(self, seq_lengths, seq_idx=None, min_length=0):
+        """Positions of every sequence covered by the multi-MUMs of the table, as the reference's `mumemto coverage` counts
+        them: uint64 [n_docs].  seq_lengths: the length of every sequence; seq_idx: one column (the others stay 0), None:
+        all of them; min_length: rows shorter than this take no part.  The table is only read."""
+        lens = np.ascontiguousarray(seq_lengths, np.int64).reshape(-1)
+        if len(lens) != self.n_docs:
+            raise MumemtoError("coverage: %d sequence lengths for a table of %d columns" % (len(lens), self.n_docs))
+        covered = np.zeros(self.n_docs, np.uint64)
+        idx = -1 if seq_idx is None else int(seq_idx)
+        if seq_idx is not None and idx < 0:
+            idx = -2                                        # (-1 means "all" to the library; a negative index is refused there)
+        _check(self.L.mmt_merged_coverage(self.engine.h, self.h, _p(lens) if len(lens) else None, C.c_int64(idx),
+                                          C.c_int64(int(min_length)), _p(covered) if len(covered) else None))
+        return covered
+
+    def coverage_runs(self):
+        """(run_begin uint64 [n_docs + 1], runs int64 [n, 2]) of the last coverage(): the maximal covered stretches of column
+        c, half-open (begin, end) and ascending, are runs[run_begin[c]:run_begin[c + 1]]"""
+        run_begin = np.zeros(self.n_docs + 1, np.uint64)
+        _check(self.L.mmt_merged_coverage_runs(self.h, _p(run_begin), None))
+        runs = np.zeros((int(run_begin[-1]), 2), np.int64)
+        if len(runs):
+            _check(self.L.mmt_merged_coverage_runs(self.h, None, _p(runs)))
+        return run_begin, runs
+
+    def coverage_runs_device(self):
+        """(address of the u64 [n_docs + 1] run offsets, address of the int64 [n, 2] runs) in HBM"""
+        a, b = C.c_void_p(), C.c_void_p()
+        _check(self.L.mmt_merged_coverage_runs_device(self.h, C.byref(a), C.byref(b)))
+        return a.value or 0, b.value or 0
+
+    def coverage_stats(self):
+        st = (C.c_double * 8)()
+        _check(self.L.mmt_merged_coverage_stats(self.h, st))
+        d = {k: float(st[i]) for i, k in enumerate(["extract_ms", "sort_ms", "scan_ms", "runs_ms"])}
+        d.update(cols_sorted=int(st[4]), cols_ascending=int(st[5]), batches=int(st[6]), runs=int(st[7]))
+        return d
+
     def text(self):
         k = C.c_size_t()
         ptr = self.L.mmt_merged_text(self.h, C.byref(k))
@@ -950,6 +994,18 @@ def find_inversions(lengths, starts, strands, max_block_gap=1000, max_length=Non
         with Merged.from_rows(eng, lengths, starts, strands) as m:
             m.collinear(max_block_gap, None)
             return m.inversions(max_length)
+    finally:
+        eng.close()
+
+
+def mum_coverage(lengths, starts, strands, seq_lengths, seq_idx=None, min_length=0, device=0):
+    """Rows on the host -> (covered uint64 [n_docs], run_begin uint64 [n_docs + 1], runs int64 [n, 2]): the positions of
+    every sequence (or of seq_idx alone) that the rows of at least min_length cover, and the covered stretches themselves."""
+    eng = Engine(device)
+    try:
+        with Merged.from_rows(eng, lengths, starts, strands) as m:
+            covered = m.coverage(seq_lengths, seq_idx, min_length)
+            return (covered,) + m.coverage_runs()
     finally:
         eng.close()
 

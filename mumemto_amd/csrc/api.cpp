@@ -21,6 +21,7 @@
 #include "fasta.hpp"
 #include "merge.hpp"
 #include "collinear.hpp"
+#include "coverage.hpp"
 #include "inversion.hpp"
 
 namespace {
@@ -103,6 +104,7 @@ struct mmt_merged {
     bool text_valid = false;
     mmt::CollinearStats coll;          // of the last mmt_merged_collinear
     mmt::InversionStats inv;           // of the last mmt_merged_inversions
+    mmt::CoverageStats cov;            // of the last mmt_merged_coverage
 };
 
 extern "C" {
@@ -827,6 +829,46 @@ int mmt_merged_inversion_stats(const mmt_merged* m, double out[8]) {
     for (int i = 0; i < 3; i++) out[i] = S.ms[i];
     out[3] = (double)S.blocks; out[4] = (double)S.cols_sorted; out[5] = (double)S.cols_ascending; out[6] = (double)S.runs;
     out[7] = (double)(m->rows.has_calls ? m->rows.n_calls : 0);
+    return 0;
+}
+// ---- coverage (coverage.cpp) ----------------------------------------------------------------
+int mmt_merged_coverage(mmt_engine* e, mmt_merged* m, const int64_t* seq_lengths, int64_t seq_idx, int64_t min_length,
+                        uint64_t* covered) {
+    if (!e || !m) return fail(1, "engine and merged rows must be non-null");
+    if (e->e.get() != m->engine) return fail(1, "the merged rows belong to another engine");
+    MMT_TRY
+    mmt::coverage(*e->e, m->rows, seq_lengths, seq_idx, min_length, &m->cov);
+    if (covered && m->rows.n_docs) std::memcpy(covered, m->rows.cov_covered.data(), m->rows.n_docs * 8);
+    MMT_CATCH
+}
+int mmt_merged_coverage_runs(const mmt_merged* m, uint64_t* run_begin, int64_t* runs) {
+    if (!m) return fail(1, "null");
+    if (!m->rows.has_coverage) return fail(3, "no coverage attached: call mmt_merged_coverage first");
+    MMT_TRY
+    const mmt::MergedRows& R = m->rows;
+    if (run_begin) std::memcpy(run_begin, R.cov_run_begin.data(), R.cov_run_begin.size() * 8);
+    const size_t n_runs = (size_t)R.cov_run_begin.back();
+    if (runs && n_runs) {
+        hipStream_t st = m->engine->stream();
+        MMT_HIP(hipSetDevice(m->engine->device()));
+        MMT_HIP(hipMemcpyAsync(runs, R.d_runs.get(), n_runs * 16, hipMemcpyDeviceToHost, st));
+        MMT_HIP(hipStreamSynchronize(st));
+    }
+    MMT_CATCH
+}
+int mmt_merged_coverage_runs_device(const mmt_merged* m, const uint64_t** run_begin, const int64_t** runs) {
+    if (!m) return fail(1, "null");
+    if (!m->rows.has_coverage) return fail(3, "no coverage attached: call mmt_merged_coverage first");
+    if (run_begin) *run_begin = m->rows.d_run_begin.get();
+    if (runs) *runs = m->rows.d_runs.get();
+    return 0;
+}
+int mmt_merged_coverage_stats(const mmt_merged* m, double out[8]) {
+    if (!m || !out) return fail(1, "null");
+    const mmt::CoverageStats& S = m->cov;
+    for (int i = 0; i < 4; i++) out[i] = S.ms[i];
+    out[4] = (double)S.cols_sorted; out[5] = (double)S.cols_ascending; out[6] = (double)S.batches;
+    out[7] = (double)(m->rows.has_coverage ? m->rows.cov_run_begin.back() : 0);
     return 0;
 }
 int mmt_merged_sort_like_direct(mmt_engine* e, mmt_merged* m) {

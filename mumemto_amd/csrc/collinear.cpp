@@ -37,6 +37,7 @@ void collinear_blocks(Engine& e, MergedRows& m, uint32_t max_break, int64_t min_
     Laps laps(st, stats ? S.ms : nullptr);
     m.has_blocks = false; m.n_blocks = 0;
     m.has_calls = false; m.n_calls = 0;
+    m.has_coverage = false;                      // (a reading of the table this call replaces)
     S.rows_in = m.n_rows;
 
     // ---- (1) MUMdata.filter_pmums + MUMdata.sort (utils.py:486-495, :323-361) -------------------------------------------

@@ -29,6 +29,12 @@ struct MergedRows {
     bool has_calls = false;
     size_t n_calls = 0;
     DevBuf<int64_t> d_calls;        // n_calls x (column, start, end, ref_start, ref_end)
+    // coverage (coverage.hpp), attached by coverage(): a reading of the table above; whatever replaces the table drops it
+    bool has_coverage = false;
+    std::vector<uint64_t> cov_covered;     // n_docs: covered positions of the column, 0 for a column not asked for
+    std::vector<uint64_t> cov_run_begin;   // n_docs + 1: the runs of column c are [cov_run_begin[c], cov_run_begin[c + 1])
+    DevBuf<uint64_t> d_run_begin;   // the same offsets in HBM
+    DevBuf<int64_t> d_runs;         // cov_run_begin[n_docs] x (begin, end), half-open
 
     MergedRows() = default;
     MergedRows(MergedRows&& o) noexcept { *this = std::move(o); }
@@ -41,6 +47,9 @@ struct MergedRows {
         d_row_block.swap(o.d_row_block); d_blocks.swap(o.d_blocks);
         has_calls = o.has_calls; n_calls = o.n_calls;
         d_calls.swap(o.d_calls);
+        has_coverage = o.has_coverage;
+        cov_covered = std::move(o.cov_covered); cov_run_begin = std::move(o.cov_run_begin);
+        d_run_begin.swap(o.d_run_begin); d_runs.swap(o.d_runs);
         return *this;
     }
 };

@@ -107,3 +107,22 @@ def write_bumbl(path, lengths, starts, strands, blocks=None):
             blocks = np.ascontiguousarray(blocks, np.uint32).reshape(-1, 2)
             f.write(np.uint64(len(blocks)).tobytes())
             f.write(blocks.tobytes())
+
+
+def read_seq_lengths(path):
+    """the length of every sequence of a PREFIX.lengths file, as the reference's get_sequence_lengths reads it
+    (mumemto/utils.py:177-207): the second field of every line, or, of a multi-FASTA file (`PATH * total` followed by the
+    `PATH name length` lines of the contigs), the sum of the third fields of a sequence's contig lines"""
+    lines = [l.split() for l in open(path).read().splitlines()]
+    if not (lines and len(lines[0]) > 1 and lines[0][1] == "*"):
+        return [int(l[1]) for l in lines]
+    out, cur = [], []
+    for l in lines:
+        if l[1] == "*":
+            if cur:
+                out.append(cur)
+            cur = []
+            continue
+        cur.append(int(l[2]))
+    out.append(cur)
+    return [sum(o) for o in out]
