@@ -380,6 +380,45 @@ MMT_API int mmt_merged_coverage_runs_device(const mmt_merged* m, const uint64_t*
 /* Of the last mmt_merged_coverage on m: out[0..3] HIP-event milliseconds of the extraction, column sorts, running maximum +
  * sum, runs; [4] columns that needed a sort, [5] columns found ascending, [6] column batches, [7] runs in all.           */
 MMT_API int mmt_merged_coverage_stats(const mmt_merged* m, double out[8]);
+/* ---- BED intervals (`mumemto bed`: mumemto/mum_to_bed.py) -----------------------------------------------------------------
+ * Callers detect these entry points by their symbols; mmt_abi_version() did not change for them.
+ * The collinear blocks and the long multi-MUMs of the table as `contig <TAB> start <TAB> end <TAB> name <TAB> strand` lines in
+ * the coordinates of the contigs (FASTA records) of a sequence.  Records of column c, in ascending order of their first row:
+ *   with blocks attached (mmt_merged_collinear, mmt_merged_set_blocks): one per block (first, last) and one per row in no
+ *     block with length >= min_singleton_length;
+ *   without: one per row with a start in c (not -1) and length >= min_singleton_length.
+ * A block whose last row is on '+' in c is [start[first], start[last] + length[last]), another one [start[last], start[first] +
+ * length[first]); a row is [start, start + length).  The strand is that of the last row.  name = the block's number, or
+ * -1 - i for a row, i = its rank among the rows with a start in c (the row number itself when no row is partial).  With
+ * ends_k = len_0 + ... + len_k over the contigs of c, the contig is the first k with ends_k > begin (a contig of length 0 is
+ * never chosen), rel_start = begin - (ends_k - len_k), rel_end = rel_start + (end - begin): an interval that runs over the end
+ * of its contig is not split.  A begin at or beyond the total gets the last contig and is counted (stats [5]).
+ *
+ * mmt_merged_bed reads the table and changes nothing of it: rows, blocks, inversion calls and coverage stay.  The contigs of
+ * column c are entries [contig_begin[c], contig_begin[c + 1]) of contig_len and name_begin; contig_begin has n_docs + 1 host
+ * entries, name_begin one entry per contig and one more: name g is names[name_begin[g] .. name_begin[g + 1]).  seq_idx >= 0:
+ * that column, -1: every column; n_records (may be null) receives the number of records.  It refuses, rc 3 and a message: a
+ * seq_idx outside [-1, n_docs), null tables, a needed column without contigs or of total length 0, a negative contig length
+ * and a name with a tab or a newline in a needed column.  Fewer than 2^32 rows.  Calling it again replaces the results;
+ * mmt_merged_collinear, mmt_merged_set_blocks and mmt_merged_sort_like_direct drop them.                                  */
+MMT_API int mmt_merged_bed(mmt_engine* e, mmt_merged* m, const uint64_t* contig_begin, const int64_t* contig_len,
+                           const uint64_t* name_begin, const char* names, int64_t seq_idx, int64_t min_singleton_length,
+                           uint64_t* n_records);
+/* record_begin receives n_docs + 1 host entries: the records of column c are [record_begin[c], record_begin[c + 1]), none for
+ * a column not asked for; records receives 5 x record_begin[n_docs] host entries: contig (within the column), rel_start,
+ * rel_end, name, strand (1 = '+').  records may be null, to ask for the sizes first.                                      */
+MMT_API int mmt_merged_bed_records(const mmt_merged* m, uint64_t* record_begin, int64_t* records);
+/* the same two arrays in HBM; owned by m                                                                               */
+MMT_API int mmt_merged_bed_records_device(const mmt_merged* m, const uint64_t** record_begin, const int64_t** records);
+/* The lines of column col of the last mmt_merged_bed, formatted on the device; the bytes live until the next call on m.
+ * Null (and a message) when no records are attached or col is out of range.                                             */
+MMT_API const char* mmt_merged_bed_text(mmt_merged* m, int64_t col, size_t* len);
+/* The same bytes to PATH.tmp, renamed to PATH when complete (a path that is no regular file, such as /dev/stdout, is written
+ * as it is).                                                                                                            */
+MMT_API int mmt_merged_bed_write_text(mmt_merged* m, int64_t col, const char* path);
+/* Of the last mmt_merged_bed on m: out[0..3] HIP-event milliseconds of select, gather, contig lookup and of the text written
+ * since; [4] records, [5] records clamped to the last contig, [6] column batches, [7] text bytes written since.          */
+MMT_API int mmt_merged_bed_stats(const mmt_merged* m, double out[8]);
 /* Re-order merged rows into the order of a direct run (lexicographic by match
  * string) using the anchor suffix ranks of the engine's last run, whose
  * document 0 must be the anchor.                              */

@@ -19,6 +19,7 @@ from .binding import (  # noqa: F401
     library_path,
     load_library,
     mum_coverage,
+    mum_to_bed,
     mumemto_mem,
     mumemto_mum,
 )

@@ -85,6 +85,8 @@ GPU_ABI_SYMBOLS = [
     "mmt_merged_blocks_device", "mmt_merged_collinear_stats", "mmt_merged_set_blocks", "mmt_merged_inversions",
     "mmt_merged_inversion_calls", "mmt_merged_inversion_calls_device", "mmt_merged_inversion_stats",
     "mmt_merged_coverage", "mmt_merged_coverage_runs", "mmt_merged_coverage_runs_device", "mmt_merged_coverage_stats",
+    "mmt_merged_bed", "mmt_merged_bed_records", "mmt_merged_bed_records_device", "mmt_merged_bed_text",
+    "mmt_merged_bed_write_text", "mmt_merged_bed_stats",
 ]
 
 
@@ -200,6 +202,14 @@ def load_library():
     L.mmt_merged_coverage_runs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.mmt_merged_coverage_runs_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.mmt_merged_coverage_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    L.mmt_merged_bed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                 C.POINTER(C.c_uint64)]
+    L.mmt_merged_bed_records.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mmt_merged_bed_records_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.mmt_merged_bed_text.restype = C.c_void_p
+    L.mmt_merged_bed_text.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_size_t)]
+    L.mmt_merged_bed_write_text.argtypes = [C.c_void_p, C.c_int64, C.c_char_p]
+    L.mmt_merged_bed_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.mmt_comm_unique_id.argtypes = [C.c_void_p]
     L.mmt_comm_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
     L.mmt_comm_destroy.argtypes = [C.c_void_p]
@@ -782,7 +792,8 @@ Engine.rows_in_direct_order = _engine_rows_in_direct_order
 class Merged:
     """A row table in the HBM of an engine's GPU (mmt_merged of mumemto_gpu.h): the result of a fold, or rows handed over
     with Merged.from_rows / Merged.from_device.  collinear() computes the collinear blocks of its rows on the device,
-    inversions() the inversion calls over them, coverage() the share of every sequence its rows cover."""
+    inversions() the inversion calls over them, coverage() the share of every sequence its rows cover, bed() the blocks and
+    rows as BED intervals in contig coordinates."""
 
     def __init__(self, engine, handle):
         self.engine, self.L, self.h = engine, engine.L, handle
@@ -963,6 +974,59 @@ class Merged:
         d.update(cols_sorted=int(st[4]), cols_ascending=int(st[5]), batches=int(st[6]), runs=int(st[7]))
         return d
 
+    def bed(self, contigs, seq_idx=None, min_singleton_length=100):
+        """BED records of the table as the reference's `mumemto bed` makes them, with the departures of mum_to_bed.py's
+        docstring: one per collinear block and per free row of at least min_singleton_length (every such row with a start in
+        the column when no blocks are attached).  contigs: (names, lengths), each one list per sequence in file order, as
+        mumsio.read_contigs returns them; seq_idx: one column, None: all of them.  Returns the number of records; the table
+        is only read."""
+        begin, lens, name_begin, blob = contig_tables(contigs)
+        if len(begin) != self.n_docs + 1:
+            raise MumemtoError("bed: contigs of %d sequences for a table of %d columns" % (len(begin) - 1, self.n_docs))
+        idx = -1 if seq_idx is None else int(seq_idx)
+        if seq_idx is not None and idx < 0:
+            idx = -2                                        # (-1 means "all" to the library; a negative index is refused there)
+        k = C.c_uint64()
+        names = np.frombuffer(blob, np.uint8) if blob else np.zeros(1, np.uint8)
+        _check(self.L.mmt_merged_bed(self.engine.h, self.h, _p(begin), _p(lens), _p(name_begin), _p(names), C.c_int64(idx),
+                                     C.c_int64(int(min_singleton_length)), C.byref(k)))
+        return int(k.value)
+
+    def bed_records(self):
+        """(record_begin uint64 [n_docs + 1], records int64 [n, 5]) of the last bed(): the records of column c are
+        records[record_begin[c]:record_begin[c + 1]] = (contig within the column, rel_start, rel_end, name, strand), name =
+        the block, or -1 - i for row i of the column"""
+        record_begin = np.zeros(self.n_docs + 1, np.uint64)
+        _check(self.L.mmt_merged_bed_records(self.h, _p(record_begin), None))
+        records = np.zeros((int(record_begin[-1]), 5), np.int64)
+        if len(records):
+            _check(self.L.mmt_merged_bed_records(self.h, None, _p(records)))
+        return record_begin, records
+
+    def bed_records_device(self):
+        """(address of the u64 [n_docs + 1] record offsets, address of the int64 [n, 5] records) in HBM"""
+        a, b = C.c_void_p(), C.c_void_p()
+        _check(self.L.mmt_merged_bed_records_device(self.h, C.byref(a), C.byref(b)))
+        return a.value or 0, b.value or 0
+
+    def bed_text(self, col):
+        """the BED lines of column col of the last bed(), formatted on the device"""
+        k = C.c_size_t()
+        ptr = self.L.mmt_merged_bed_text(self.h, C.c_int64(int(col)), C.byref(k))
+        if not ptr:
+            raise MumemtoError("libmumemto: %s" % self.L.mmt_last_error().decode(errors="replace"))
+        return _bytes_at(ptr, k.value)
+
+    def write_bed(self, col, path):
+        _check(self.L.mmt_merged_bed_write_text(self.h, C.c_int64(int(col)), os.fsencode(path)))
+
+    def bed_stats(self):
+        st = (C.c_double * 8)()
+        _check(self.L.mmt_merged_bed_stats(self.h, st))
+        d = {k: float(st[i]) for i, k in enumerate(["select_ms", "gather_ms", "lookup_ms", "text_ms"])}
+        d.update(records=int(st[4]), clamped=int(st[5]), batches=int(st[6]), text_bytes=int(st[7]))
+        return d
+
     def text(self):
         k = C.c_size_t()
         ptr = self.L.mmt_merged_text(self.h, C.byref(k))
@@ -1006,6 +1070,44 @@ def mum_coverage(lengths, starts, strands, seq_lengths, seq_idx=None, min_length
         with Merged.from_rows(eng, lengths, starts, strands) as m:
             covered = m.coverage(seq_lengths, seq_idx, min_length)
             return (covered,) + m.coverage_runs()
+    finally:
+        eng.close()
+
+
+def contig_tables(contigs):
+    """(names, lengths), one list per sequence -> the four tables of mmt_merged_bed: contig_begin u64 [n_seqs + 1], contig_len
+    i64 and name_begin u64 [n_contigs + 1] over all contigs, and the names as one byte blob"""
+    names, lengths = contigs
+    if len(names) != len(lengths) or any(len(a) != len(b) for a, b in zip(names, lengths)):
+        raise MumemtoError("bed: names and lengths of the contigs do not match")
+    begin = np.zeros(len(names) + 1, np.uint64)
+    begin[1:] = np.cumsum([len(x) for x in names], dtype=np.uint64)
+    flat = [n if isinstance(n, bytes) else str(n).encode() for seq in names for n in seq]
+    for n in flat:
+        if b"\t" in n or b"\n" in n:
+            raise MumemtoError("bed: the contig name %r contains a tab or a newline" % n)
+    name_begin = np.zeros(len(flat) + 1, np.uint64)
+    name_begin[1:] = np.cumsum([len(n) for n in flat], dtype=np.uint64)
+    lens = np.ascontiguousarray([int(v) for seq in lengths for v in seq] + [0], np.int64)
+    return begin, lens, name_begin, b"".join(flat)
+
+
+def mum_to_bed(lengths, starts, strands, contigs, blocks=None, seq_idx=None, min_singleton_length=100, max_block_gap=None,
+               device=0):
+    """Rows on the host -> (record_begin uint64 [n_docs + 1], records int64 [n, 5], texts): the BED records of every sequence
+    (or of seq_idx alone) and their lines, {column: bytes}.  blocks: a block list (n_blocks, 2) for rows that are the
+    filtered, sorted table; max_block_gap: compute the blocks first, as collinear_blocks does; neither: every row of at least
+    min_singleton_length that has a start in the column."""
+    eng = Engine(device)
+    try:
+        with Merged.from_rows(eng, lengths, starts, strands) as m:
+            if blocks is not None:
+                m.set_blocks(blocks)
+            elif max_block_gap is not None:
+                m.collinear(max_block_gap, None)
+            m.bed(contigs, seq_idx, min_singleton_length)
+            cols = range(m.n_docs) if seq_idx is None else [int(seq_idx)]
+            return m.bed_records() + ({c: m.bed_text(c) for c in cols},)
     finally:
         eng.close()
 

@@ -21,6 +21,7 @@
 #include "fasta.hpp"
 #include "merge.hpp"
 #include "collinear.hpp"
+#include "bed.hpp"
 #include "coverage.hpp"
 #include "inversion.hpp"
 
@@ -105,6 +106,8 @@ struct mmt_merged {
     mmt::CollinearStats coll;          // of the last mmt_merged_collinear
     mmt::InversionStats inv;           // of the last mmt_merged_inversions
     mmt::CoverageStats cov;            // of the last mmt_merged_coverage
+    mmt::BedStats bed;                 // of the last mmt_merged_bed, and of the text written since
+    std::string bed_text;              // of the last mmt_merged_bed_text
 };
 
 extern "C" {
@@ -869,6 +872,62 @@ int mmt_merged_coverage_stats(const mmt_merged* m, double out[8]) {
     for (int i = 0; i < 4; i++) out[i] = S.ms[i];
     out[4] = (double)S.cols_sorted; out[5] = (double)S.cols_ascending; out[6] = (double)S.batches;
     out[7] = (double)(m->rows.has_coverage ? m->rows.cov_run_begin.back() : 0);
+    return 0;
+}
+// ---- BED intervals (bed.cpp) ----------------------------------------------------------------
+int mmt_merged_bed(mmt_engine* e, mmt_merged* m, const uint64_t* contig_begin, const int64_t* contig_len,
+                   const uint64_t* name_begin, const char* names, int64_t seq_idx, int64_t min_singleton_length,
+                   uint64_t* n_records) {
+    if (!e || !m) return fail(1, "engine and merged rows must be non-null");
+    if (e->e.get() != m->engine) return fail(1, "the merged rows belong to another engine");
+    MMT_TRY
+    mmt::bed(*e->e, m->rows, contig_begin, contig_len, name_begin, names, seq_idx, min_singleton_length, &m->bed);
+    if (n_records) *n_records = m->rows.bed_record_begin.back();
+    MMT_CATCH
+}
+int mmt_merged_bed_records(const mmt_merged* m, uint64_t* record_begin, int64_t* records) {
+    if (!m) return fail(1, "null");
+    if (!m->rows.has_bed) return fail(3, "no BED records attached: call mmt_merged_bed first");
+    MMT_TRY
+    const mmt::MergedRows& R = m->rows;
+    if (record_begin) std::memcpy(record_begin, R.bed_record_begin.data(), R.bed_record_begin.size() * 8);
+    const size_t n_records = (size_t)R.bed_record_begin.back();
+    if (records && n_records) {
+        hipStream_t st = m->engine->stream();
+        MMT_HIP(hipSetDevice(m->engine->device()));
+        MMT_HIP(hipMemcpyAsync(records, R.d_bed_records.get(), n_records * 40, hipMemcpyDeviceToHost, st));
+        MMT_HIP(hipStreamSynchronize(st));
+    }
+    MMT_CATCH
+}
+int mmt_merged_bed_records_device(const mmt_merged* m, const uint64_t** record_begin, const int64_t** records) {
+    if (!m) return fail(1, "null");
+    if (!m->rows.has_bed) return fail(3, "no BED records attached: call mmt_merged_bed first");
+    if (record_begin) *record_begin = m->rows.d_bed_record_begin.get();
+    if (records) *records = m->rows.d_bed_records.get();
+    return 0;
+}
+const char* mmt_merged_bed_text(mmt_merged* m, int64_t col, size_t* len) {
+    if (len) *len = 0;
+    if (!m) { fail(1, "null"); return nullptr; }
+    try { m->bed_text = mmt::bed_text(*m->engine, m->rows, col, &m->bed); }
+    catch (const std::exception& ex) { fail(3, ex.what()); return nullptr; }
+    if (len) *len = m->bed_text.size();
+    return m->bed_text.data();
+}
+int mmt_merged_bed_write_text(mmt_merged* m, int64_t col, const char* path) {
+    if (!m || !path) return fail(1, "null");
+    MMT_TRY
+    mmt::bed_write_text(*m->engine, m->rows, col, path, &m->bed);
+    MMT_CATCH
+}
+int mmt_merged_bed_stats(const mmt_merged* m, double out[8]) {
+    if (!m || !out) return fail(1, "null");
+    const mmt::BedStats& S = m->bed;
+    const bool has = m->rows.has_bed;
+    for (int i = 0; i < 4; i++) out[i] = S.ms[i];
+    out[4] = (double)(has ? S.records : 0); out[5] = (double)(has ? S.clamped : 0); out[6] = (double)S.batches;
+    out[7] = (double)S.text_bytes;
     return 0;
 }
 int mmt_merged_sort_like_direct(mmt_engine* e, mmt_merged* m) {

@@ -66,6 +66,7 @@ void set_blocks(Engine& e, MergedRows& m, const uint32_t* lr, uint64_t n_blocks)
     m.n_blocks = B;
     m.has_blocks = true;
     m.has_calls = false; m.n_calls = 0;
+    m.has_bed = false;                           // (records of the blocks this call replaces)
 }
 
 void inversion_calls(Engine& e, MergedRows& m, int64_t max_length, InversionStats* stats) {

@@ -456,6 +456,7 @@ void sort_like_direct(Engine& e, MergedRows& m) {
     m.has_blocks = false; m.n_blocks = 0;       // (blocks are row ranges of the order they were computed in)
     m.has_calls = false; m.n_calls = 0;
     m.has_coverage = false;
+    m.has_bed = false;
 }
 
 // the fourth field of the text: the collinear block of every row, when blocks are attached (collinear.hpp)

@@ -35,6 +35,14 @@ struct MergedRows {
     std::vector<uint64_t> cov_run_begin;   // n_docs + 1: the runs of column c are [cov_run_begin[c], cov_run_begin[c + 1])
     DevBuf<uint64_t> d_run_begin;   // the same offsets in HBM
     DevBuf<int64_t> d_runs;         // cov_run_begin[n_docs] x (begin, end), half-open
+    // BED records (bed.hpp), attached by bed(): a reading of the table and of its blocks; whatever replaces either drops them
+    bool has_bed = false;
+    std::vector<uint64_t> bed_record_begin;   // n_docs + 1: the records of column c are [bed_record_begin[c], bed_record_begin[c + 1])
+    std::vector<uint64_t> bed_contig_begin;   // n_docs + 1: the contigs of column c among all contigs
+    DevBuf<uint64_t> d_bed_record_begin;      // the same offsets in HBM
+    DevBuf<int64_t> d_bed_records;  // bed_record_begin[n_docs] x (contig, rel_start, rel_end, name, strand)
+    DevBuf<uint64_t> d_bed_name_begin;        // per contig (and one more): its name in d_bed_names
+    DevBuf<char> d_bed_names;
 
     MergedRows() = default;
     MergedRows(MergedRows&& o) noexcept { *this = std::move(o); }
@@ -50,6 +58,10 @@ struct MergedRows {
         has_coverage = o.has_coverage;
         cov_covered = std::move(o.cov_covered); cov_run_begin = std::move(o.cov_run_begin);
         d_run_begin.swap(o.d_run_begin); d_runs.swap(o.d_runs);
+        has_bed = o.has_bed;
+        bed_record_begin = std::move(o.bed_record_begin); bed_contig_begin = std::move(o.bed_contig_begin);
+        d_bed_record_begin.swap(o.d_bed_record_begin); d_bed_records.swap(o.d_bed_records);
+        d_bed_name_begin.swap(o.d_bed_name_begin); d_bed_names.swap(o.d_bed_names);
         return *this;
     }
 };

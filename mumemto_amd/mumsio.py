@@ -126,3 +126,27 @@ def read_seq_lengths(path):
         cur.append(int(l[2]))
     out.append(cur)
     return [sum(o) for o in out]
+
+
+def read_contigs(path):
+    """(names, lengths) of the contigs of a multi-FASTA PREFIX.lengths file, one list per sequence in file order, from the lines
+    the reference's get_sequence_lengths(multilengths=True) and get_contig_names read (mumemto/utils.py:180-192,221-247): a
+    `PATH * total` line begins a sequence, the `PATH name length` lines behind it are its contigs.  As there, a `*` line
+    directly behind another one begins no sequence of its own.  A plain `PATH length` file is refused: it has no contigs."""
+    lines = [l.split() for l in open(path).read().splitlines()]
+    if not (lines and len(lines[0]) > 1 and lines[0][1] == "*"):
+        raise ValueError("%s has no contig lines: the lengths file must come from a multi-FASTA-aware run "
+                         "(`PATH * total` lines followed by `PATH name length` lines)" % path)
+    names, lengths, cur_n, cur_l = [], [], [], []
+    for l in lines:
+        if l[1] == "*":
+            if cur_n:
+                names.append(cur_n)
+                lengths.append(cur_l)
+            cur_n, cur_l = [], []
+            continue
+        cur_n.append(l[1])
+        cur_l.append(int(l[2]))
+    names.append(cur_n)
+    lengths.append(cur_l)
+    return names, lengths
