@@ -419,6 +419,41 @@ MMT_API int mmt_merged_bed_write_text(mmt_merged* m, int64_t col, const char* pa
 /* Of the last mmt_merged_bed on m: out[0..3] HIP-event milliseconds of select, gather, contig lookup and of the text written
  * since; [4] records, [5] records clamped to the last contig, [6] column batches, [7] text bytes written since.          */
 MMT_API int mmt_merged_bed_stats(const mmt_merged* m, double out[8]);
+/* ---- contig labels (`mumemto label`: mumemto/get_sequence_info.py) ----------------------------------------------------------
+ * Callers detect these entry points by their symbols; mmt_abi_version() did not change for them.
+ * Every start of the table also as (contig, offset inside that contig), and the table as lines of six fields:
+ *   LEN <TAB> s_0,...,s_{N-1} <TAB> +|-,... <TAB> BLOCK <TAB> c_0,...,c_{N-1} <TAB> rel_0,...,rel_{N-1}
+ * one per row, in row order, nothing filtered.  With ends_k = len_0 + ... + len_k over the contigs of column c, cell (r, c) with
+ * start s gets the first k with ends_k > s (a contig of length 0 is never chosen) and rel = s - (ends_k - len_k); an absent
+ * cell (s == -1) gets contig 0 and rel -1, and is printed as -1 in fields 2 and 6.  BLOCK is * for a table without blocks, else
+ * the number of the row's block among those attached when the text is asked for (mmt_merged_collinear, mmt_merged_set_blocks),
+ * or -.  Field 5 holds the decimal contigs, or with use_names their names (the name of contig 0 for an absent cell).
+ *
+ * mmt_merged_label reads the table and changes nothing of it: rows, blocks, inversion calls, coverage and BED records stay;
+ * partial rows and a table without rows (0 bytes) are legal.  The contig tables have the shape mmt_merged_bed takes, for every
+ * column; name_begin and names are read with use_names only and may be null without.  text_bytes (may be null) receives the
+ * length of the text.  It refuses, rc 3 and a message: null tables, a column without contigs or of total length 0, a negative
+ * contig length, with use_names a name with a tab, a newline or a comma, and a start at or beyond the total of its sequence:
+ * the message names the first such (row, column) in row-major order, its start and the total.  After a refused call no
+ * labels are attached, those of an earlier call included.
+ * Fewer than 2^32 rows.  Calling it again replaces the results; mmt_merged_collinear and mmt_merged_sort_like_direct drop
+ * them, mmt_merged_set_blocks keeps them.  Before mmt_merged_label the accessors below return rc 3 (null for the text).   */
+MMT_API int mmt_merged_label(mmt_engine* e, mmt_merged* m, const uint64_t* contig_begin, const int64_t* contig_len,
+                             const uint64_t* name_begin, const char* names, int use_names, uint64_t* text_bytes);
+/* contig and rel receive n_rows x n_docs host entries each, row-major like the table; either may be null              */
+MMT_API int mmt_merged_label_cells(const mmt_merged* m, uint32_t* contig, int64_t* rel);
+/* the same two arrays in HBM; owned by m                                                                               */
+MMT_API int mmt_merged_label_cells_device(const mmt_merged* m, const uint32_t** contig, const int64_t** rel);
+/* The lines of the last mmt_merged_label, formatted on the device; the bytes live until the next call on m.  Null (and a
+ * message) when no labels are attached.                                                                                 */
+MMT_API const char* mmt_merged_label_text(mmt_merged* m, size_t* len);
+/* The same bytes, formatted and written in pieces of whole rows, to PATH.tmp, renamed to PATH when complete (a path that is no
+ * regular file, such as /dev/stdout, is written as it is).                                                              */
+MMT_API int mmt_merged_label_write_text(mmt_merged* m, const char* path);
+/* Of the last mmt_merged_label on m and of the text asked for since: out[0..3] HIP-event milliseconds of the lookup, of measure
+ * + prefix sum, of the write, and of the copies to the host + the wait for the file; [4] cells, [5] absent cells, [6] columns
+ * whose contig ends were searched in HBM rather than LDS, [7] bytes of the text as last measured.                       */
+MMT_API int mmt_merged_label_stats(const mmt_merged* m, double out[8]);
 /* Re-order merged rows into the order of a direct run (lexicographic by match
  * string) using the anchor suffix ranks of the engine's last run, whose
  * document 0 must be the anchor.                              */

@@ -16,6 +16,7 @@ from .binding import (  # noqa: F401
     Params,
     exchange_digest,
     find_inversions,
+    get_sequence_info,
     library_path,
     load_library,
     mum_coverage,

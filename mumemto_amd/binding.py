@@ -87,6 +87,8 @@ GPU_ABI_SYMBOLS = [
     "mmt_merged_coverage", "mmt_merged_coverage_runs", "mmt_merged_coverage_runs_device", "mmt_merged_coverage_stats",
     "mmt_merged_bed", "mmt_merged_bed_records", "mmt_merged_bed_records_device", "mmt_merged_bed_text",
     "mmt_merged_bed_write_text", "mmt_merged_bed_stats",
+    "mmt_merged_label", "mmt_merged_label_cells", "mmt_merged_label_cells_device", "mmt_merged_label_text",
+    "mmt_merged_label_write_text", "mmt_merged_label_stats",
 ]
 
 
@@ -210,6 +212,14 @@ def load_library():
     L.mmt_merged_bed_text.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_size_t)]
     L.mmt_merged_bed_write_text.argtypes = [C.c_void_p, C.c_int64, C.c_char_p]
     L.mmt_merged_bed_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    L.mmt_merged_label.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                   C.POINTER(C.c_uint64)]
+    L.mmt_merged_label_cells.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mmt_merged_label_cells_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.mmt_merged_label_text.restype = C.c_void_p
+    L.mmt_merged_label_text.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
+    L.mmt_merged_label_write_text.argtypes = [C.c_void_p, C.c_char_p]
+    L.mmt_merged_label_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.mmt_comm_unique_id.argtypes = [C.c_void_p]
     L.mmt_comm_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
     L.mmt_comm_destroy.argtypes = [C.c_void_p]
@@ -793,7 +803,7 @@ class Merged:
     """A row table in the HBM of an engine's GPU (mmt_merged of mumemto_gpu.h): the result of a fold, or rows handed over
     with Merged.from_rows / Merged.from_device.  collinear() computes the collinear blocks of its rows on the device,
     inversions() the inversion calls over them, coverage() the share of every sequence its rows cover, bed() the blocks and
-    rows as BED intervals in contig coordinates."""
+    rows as BED intervals in contig coordinates, label() every start as (contig, offset inside it)."""
 
     def __init__(self, engine, handle):
         self.engine, self.L, self.h = engine, engine.L, handle
@@ -1027,6 +1037,52 @@ class Merged:
         d.update(records=int(st[4]), clamped=int(st[5]), batches=int(st[6]), text_bytes=int(st[7]))
         return d
 
+    def label(self, contigs, names=False):
+        """Every start of the table as (contig, offset inside that contig), as the reference's `mumemto label` gives them, with
+        the departures of get_sequence_info.py's docstring.  contigs: (names, lengths), each one list per sequence in file
+        order, as mumsio.read_contigs returns them; names: the text carries the contig names instead of their numbers.
+        Returns the length of the text; the table is only read."""
+        begin, lens, name_begin, blob = contig_tables(contigs, check_names=False)
+        if len(begin) != self.n_docs + 1:
+            raise MumemtoError("label: contigs of %d sequences for a table of %d columns" % (len(begin) - 1, self.n_docs))
+        k = C.c_uint64()
+        blob = np.frombuffer(blob, np.uint8) if blob else np.zeros(1, np.uint8)
+        _check(self.L.mmt_merged_label(self.engine.h, self.h, _p(begin), _p(lens), _p(name_begin), _p(blob),
+                                       C.c_int(1 if names else 0), C.byref(k)))
+        return int(k.value)
+
+    def label_cells(self):
+        """(contig uint32 [n, N], rel int64 [n, N]) of the last label(); an absent cell is (0, -1)"""
+        n, nd = self.n_rows, self.n_docs
+        contig = np.zeros((n, nd), np.uint32)
+        rel = np.zeros((n, nd), np.int64)
+        _check(self.L.mmt_merged_label_cells(self.h, _p(contig) if contig.size else None, _p(rel) if rel.size else None))
+        return contig, rel
+
+    def label_cells_device(self):
+        """(address of the u32 [n, N] contigs, address of the int64 [n, N] offsets) in HBM"""
+        a, b = C.c_void_p(), C.c_void_p()
+        _check(self.L.mmt_merged_label_cells_device(self.h, C.byref(a), C.byref(b)))
+        return a.value or 0, b.value or 0
+
+    def label_text(self):
+        """the labelled lines of the last label(), formatted on the device, with the blocks attached now"""
+        k = C.c_size_t()
+        ptr = self.L.mmt_merged_label_text(self.h, C.byref(k))
+        if not ptr:
+            raise MumemtoError("libmumemto: %s" % self.L.mmt_last_error().decode(errors="replace"))
+        return _bytes_at(ptr, k.value)
+
+    def write_label(self, path):
+        _check(self.L.mmt_merged_label_write_text(self.h, os.fsencode(path)))
+
+    def label_stats(self):
+        st = (C.c_double * 8)()
+        _check(self.L.mmt_merged_label_stats(self.h, st))
+        d = {k: float(st[i]) for i, k in enumerate(["lookup_ms", "measure_ms", "write_ms", "copy_ms"])}
+        d.update(cells=int(st[4]), absent=int(st[5]), hbm_columns=int(st[6]), text_bytes=int(st[7]))
+        return d
+
     def text(self):
         k = C.c_size_t()
         ptr = self.L.mmt_merged_text(self.h, C.byref(k))
@@ -1074,16 +1130,17 @@ def mum_coverage(lengths, starts, strands, seq_lengths, seq_idx=None, min_length
         eng.close()
 
 
-def contig_tables(contigs):
+def contig_tables(contigs, check_names=True):
     """(names, lengths), one list per sequence -> the four tables of mmt_merged_bed: contig_begin u64 [n_seqs + 1], contig_len
-    i64 and name_begin u64 [n_contigs + 1] over all contigs, and the names as one byte blob"""
+    i64 and name_begin u64 [n_contigs + 1] over all contigs, and the names as one byte blob; check_names=False leaves the
+    judgement of the names to the library (mmt_merged_label looks at them only when it prints them)"""
     names, lengths = contigs
     if len(names) != len(lengths) or any(len(a) != len(b) for a, b in zip(names, lengths)):
         raise MumemtoError("bed: names and lengths of the contigs do not match")
     begin = np.zeros(len(names) + 1, np.uint64)
     begin[1:] = np.cumsum([len(x) for x in names], dtype=np.uint64)
     flat = [n if isinstance(n, bytes) else str(n).encode() for seq in names for n in seq]
-    for n in flat:
+    for n in flat if check_names else ():
         if b"\t" in n or b"\n" in n:
             raise MumemtoError("bed: the contig name %r contains a tab or a newline" % n)
     name_begin = np.zeros(len(flat) + 1, np.uint64)
@@ -1108,6 +1165,21 @@ def mum_to_bed(lengths, starts, strands, contigs, blocks=None, seq_idx=None, min
             m.bed(contigs, seq_idx, min_singleton_length)
             cols = range(m.n_docs) if seq_idx is None else [int(seq_idx)]
             return m.bed_records() + ({c: m.bed_text(c) for c in cols},)
+    finally:
+        eng.close()
+
+
+def get_sequence_info(lengths, starts, strands, contigs, blocks=None, names=False, device=0):
+    """Rows on the host -> (contig uint32 [n, N], rel int64 [n, N], text): every start as (contig, offset inside that contig) and
+    the six-field lines of `mumemto label`.  blocks: a block list (n_blocks, 2) for rows that are the filtered, sorted table
+    (field 4 is then the row's block or `-`, `*` without); names: field 5 holds the contig names."""
+    eng = Engine(device)
+    try:
+        with Merged.from_rows(eng, lengths, starts, strands) as m:
+            if blocks is not None:
+                m.set_blocks(blocks)
+            m.label(contigs, names)
+            return m.label_cells() + (m.label_text(),)
     finally:
         eng.close()
 

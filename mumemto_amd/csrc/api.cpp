@@ -22,6 +22,7 @@
 #include "merge.hpp"
 #include "collinear.hpp"
 #include "bed.hpp"
+#include "label.hpp"
 #include "coverage.hpp"
 #include "inversion.hpp"
 
@@ -108,6 +109,8 @@ struct mmt_merged {
     mmt::CoverageStats cov;            // of the last mmt_merged_coverage
     mmt::BedStats bed;                 // of the last mmt_merged_bed, and of the text written since
     std::string bed_text;              // of the last mmt_merged_bed_text
+    mmt::LabelStats label;             // of the last mmt_merged_label, and of the text written since
+    std::string label_text;            // of the last mmt_merged_label_text
 };
 
 extern "C" {
@@ -928,6 +931,61 @@ int mmt_merged_bed_stats(const mmt_merged* m, double out[8]) {
     for (int i = 0; i < 4; i++) out[i] = S.ms[i];
     out[4] = (double)(has ? S.records : 0); out[5] = (double)(has ? S.clamped : 0); out[6] = (double)S.batches;
     out[7] = (double)S.text_bytes;
+    return 0;
+}
+// ---- contig labels (label.cpp) --------------------------------------------------------------
+int mmt_merged_label(mmt_engine* e, mmt_merged* m, const uint64_t* contig_begin, const int64_t* contig_len,
+                     const uint64_t* name_begin, const char* names, int use_names, uint64_t* text_bytes) {
+    if (!e || !m) return fail(1, "engine and merged rows must be non-null");
+    if (e->e.get() != m->engine) return fail(1, "the merged rows belong to another engine");
+    MMT_TRY
+    m->label_text.clear();
+    mmt::label(*e->e, m->rows, contig_begin, contig_len, name_begin, names, use_names != 0, &m->label);
+    if (text_bytes) *text_bytes = m->label.text_bytes;
+    MMT_CATCH
+}
+int mmt_merged_label_cells(const mmt_merged* m, uint32_t* contig, int64_t* rel) {
+    if (!m) return fail(1, "null");
+    if (!m->rows.has_label) return fail(3, "no labels attached: call mmt_merged_label first");
+    MMT_TRY
+    const size_t cells = m->rows.n_rows * m->rows.n_docs;
+    if (cells) {
+        hipStream_t st = m->engine->stream();
+        MMT_HIP(hipSetDevice(m->engine->device()));
+        if (contig) MMT_HIP(hipMemcpyAsync(contig, m->rows.d_label_contig.get(), cells * 4, hipMemcpyDeviceToHost, st));
+        if (rel) MMT_HIP(hipMemcpyAsync(rel, m->rows.d_label_rel.get(), cells * 8, hipMemcpyDeviceToHost, st));
+        MMT_HIP(hipStreamSynchronize(st));
+    }
+    MMT_CATCH
+}
+int mmt_merged_label_cells_device(const mmt_merged* m, const uint32_t** contig, const int64_t** rel) {
+    if (!m) return fail(1, "null");
+    if (!m->rows.has_label) return fail(3, "no labels attached: call mmt_merged_label first");
+    if (contig) *contig = m->rows.d_label_contig.get();
+    if (rel) *rel = m->rows.d_label_rel.get();
+    return 0;
+}
+const char* mmt_merged_label_text(mmt_merged* m, size_t* len) {
+    if (len) *len = 0;
+    if (!m) { fail(1, "null"); return nullptr; }
+    try { m->label_text = mmt::label_text(*m->engine, m->rows, &m->label); }
+    catch (const std::exception& ex) { fail(3, ex.what()); return nullptr; }
+    if (len) *len = m->label_text.size();
+    return m->label_text.data();
+}
+int mmt_merged_label_write_text(mmt_merged* m, const char* path) {
+    if (!m || !path) return fail(1, "null");
+    MMT_TRY
+    mmt::label_write_text(*m->engine, m->rows, path, &m->label);
+    MMT_CATCH
+}
+int mmt_merged_label_stats(const mmt_merged* m, double out[8]) {
+    if (!m || !out) return fail(1, "null");
+    const mmt::LabelStats& S = m->label;
+    const bool has = m->rows.has_label;
+    for (int i = 0; i < 4; i++) out[i] = S.ms[i];
+    out[4] = (double)(has ? S.cells : 0); out[5] = (double)(has ? S.absent : 0); out[6] = (double)(has ? S.hbm_columns : 0);
+    out[7] = (double)(has ? S.text_bytes : 0);
     return 0;
 }
 int mmt_merged_sort_like_direct(mmt_engine* e, mmt_merged* m) {

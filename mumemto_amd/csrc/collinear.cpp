@@ -39,6 +39,7 @@ void collinear_blocks(Engine& e, MergedRows& m, uint32_t max_break, int64_t min_
     m.has_calls = false; m.n_calls = 0;
     m.has_coverage = false;                      // (a reading of the table this call replaces)
     m.has_bed = false;
+    m.has_label = false;
     S.rows_in = m.n_rows;
 
     // ---- (1) MUMdata.filter_pmums + MUMdata.sort (utils.py:486-495, :323-361) -------------------------------------------

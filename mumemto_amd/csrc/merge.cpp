@@ -457,6 +457,7 @@ void sort_like_direct(Engine& e, MergedRows& m) {
     m.has_calls = false; m.n_calls = 0;
     m.has_coverage = false;
     m.has_bed = false;
+    m.has_label = false;
 }
 
 // the fourth field of the text: the collinear block of every row, when blocks are attached (collinear.hpp)

@@ -43,6 +43,13 @@ struct MergedRows {
     DevBuf<int64_t> d_bed_records;  // bed_record_begin[n_docs] x (contig, rel_start, rel_end, name, strand)
     DevBuf<uint64_t> d_bed_name_begin;        // per contig (and one more): its name in d_bed_names
     DevBuf<char> d_bed_names;
+    // contig labels (label.hpp), attached by label(): a reading of the table; whatever replaces the table drops them, new blocks do not
+    bool has_label = false, label_names = false;   // label_names: the text carries contig names, not their numbers
+    DevBuf<uint32_t> d_label_contig;          // n_rows * n_docs: the contig of the start within its column
+    DevBuf<int64_t> d_label_rel;              // n_rows * n_docs: the start inside that contig, -1 for an absent cell
+    DevBuf<uint64_t> d_label_contig_begin;    // n_docs + 1: the contigs of column c among all contigs
+    DevBuf<uint64_t> d_label_name_begin;      // per contig (and one more): its name in d_label_names (with label_names)
+    DevBuf<char> d_label_names;
 
     MergedRows() = default;
     MergedRows(MergedRows&& o) noexcept { *this = std::move(o); }
@@ -62,6 +69,10 @@ struct MergedRows {
         bed_record_begin = std::move(o.bed_record_begin); bed_contig_begin = std::move(o.bed_contig_begin);
         d_bed_record_begin.swap(o.d_bed_record_begin); d_bed_records.swap(o.d_bed_records);
         d_bed_name_begin.swap(o.d_bed_name_begin); d_bed_names.swap(o.d_bed_names);
+        has_label = o.has_label; label_names = o.label_names;
+        d_label_contig.swap(o.d_label_contig); d_label_rel.swap(o.d_label_rel);
+        d_label_contig_begin.swap(o.d_label_contig_begin); d_label_name_begin.swap(o.d_label_name_begin);
+        d_label_names.swap(o.d_label_names);
         return *this;
     }
 };
