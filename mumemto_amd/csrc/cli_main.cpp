@@ -977,8 +977,17 @@ int main(int argc, char** argv) {
             js << "], \"pfp_ms\": [";
             for (int i = 0; i < 8; i++) js << (i ? ", " : "") << pm[i];
             js << "], \"heap_peak_bytes\": " << heap.peak << ", \"heap_mapped_bytes\": " << heap.mapped
-               << ", \"heap_map_seconds\": " << heap.map_seconds << ", \"seconds_since_start\": " << secs_since(g_start)
-               << "}\n";
+               << ", \"heap_map_seconds\": " << heap.map_seconds << ", \"seconds_since_start\": " << secs_since(g_start);
+            // the text sink's instrument (piece_writer.hpp), milliseconds: zeros when the run had no sink
+            const PieceWriter::Stats& ss = eng.text_sink_stats();
+            js << ", \"sink\": {\"bytes\": " << ss.bytes << ", \"pieces\": " << ss.pieces << ", \"helper_write_ms\": " << ss.write_s * 1e3
+               << ", \"helper_queue_empty_ms\": " << ss.wait_queue_s * 1e3 << ", \"helper_copy_event_ms\": " << ss.wait_event_s * 1e3
+               << ", \"helper_blocks_ms\": " << ss.ring_s * 1e3 << ", \"blocks_made\": " << ss.blocks_made
+               << ", \"helper_earlier_file_ms\": " << ss.retire_s * 1e3
+               << ", \"room_wait_written_ms\": " << ss.room_wait_s * 1e3 << ", \"room_wait_new_block_ms\": " << ss.room_create_s * 1e3
+               << ", \"close_join_ms\": " << ss.join_s * 1e3 << ", \"close_commit_ms\": " << ss.commit_s * 1e3
+               << ", \"tail_after_last_copy_ms\": " << eng.text_sink_tail_seconds() * 1e3 << "}";
+            js << "}\n";
         }
         log_line("build_main", "Found " + std::to_string(R.n_rows) + " matches!");
         if (o.keep_temp) write_pfp_files();         // -K: keep PREFIX.dict / PREFIX.parse

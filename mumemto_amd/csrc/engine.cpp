@@ -913,7 +913,15 @@ void Engine::sink_open() {
     if (!rows_.mum_mode && !sink_discard_) return;          // (a MEM run that keeps its rows writes its file at the end, as before)
     // ("/dev/null": the bytes are formatted, copied out, digested and dropped -- a full-size test run whose 66 GB of rows the
     // box has no room for)
-    sink_writer_.open(sink_path_, device_, sw::on(sw::MMT_SINK_DIGEST));
+    // What is known now is the text.  A row of PREFIX.mums costs ~11 bytes per document and the text holds two strands of every
+    // document: one output byte per 12 characters of text stands for a row every ~66 bases of a document (the 94 x 64 Mbp
+    // stand-in has one every 73).  The estimate only decides how many blocks of the ring are page-locked during the sort: a
+    // job of kilobases gets one, a denser table than expected asks for the others when it needs them.
+    PieceWriter::Early early;
+    early.expected_bytes = std::max<uint64_t>(n_ / SINK_TEXT_PER_BYTE, 1);
+    early.retire_old = true;
+    sink_writer_.open(sink_path_, device_, sw::on(sw::MMT_SINK_DIGEST), early);
+    sink_tail_s_ = 0;
     sink_rows_done_ = 0;
     sink_pieces_ = 0;
     if (!sink_stream_) {
@@ -964,6 +972,10 @@ void Engine::sink_flush(ScanState& S) {
 void Engine::sink_close(bool ok) {
     if (!sink_writer_.active()) return;
     (void)hipStreamSynchronize(sink_stream_);
+    // the last piece has left the device: from here to the return of close() the GPU has nothing left to do
+    const auto gpu_done = std::chrono::steady_clock::now();
+    struct Tail { Engine* e; std::chrono::steady_clock::time_point t0;
+                  ~Tail() { e->sink_tail_s_ = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); } } tail{this, gpu_done};
     sink_writer_.close(ok);
     sink_written_path_ = sink_path_;
     sink_discarded_ = sink_discard_;
@@ -1261,6 +1273,11 @@ void Engine::run(const mmt_params& p) {
     if (kind == 3 || kind == 4) pfp_want_guided_ = true;
     run_slices_ = text_passes_ = batches_ = 0; staged_ = false;
     stream_min_len_ = p.min_match_len;
+    // the sink opens before the tables of the parse are built: its helper thread has the whole sort to page-lock the ring and
+    // to remove the file of an earlier run, and neither waits at the end of the run
+    sink_open();
+    struct SinkGuard { Engine* e; bool armed = true;
+                       ~SinkGuard() { if (armed) { try { e->sink_close(false); } catch (...) {} } } } sink_guard{this};
     ev_[1]->start(stream_);
     // (the stream does not depend on the parameters of the parse: a producer named without them gets the automatic ones)
     pfp_prepare(producer_ == 0 || !pfp_w_ ? auto_w : pfp_w_, producer_ == 0 || !pfp_p_ ? auto_p : pfp_p_);
@@ -1282,14 +1299,9 @@ void Engine::run(const mmt_params& p) {
     ScanState S;
     scan_begin(p, S);
     streamed_ = true;
-    sink_open();
-    try {
-        if (pfp_->guided) guided_stream(S, p); else pfp_stream(S, p);
-        sink_flush(S);
-    } catch (...) {
-        try { sink_close(false); } catch (...) {}
-        throw;
-    }
+    if (pfp_->guided) guided_stream(S, p); else pfp_stream(S, p);
+    sink_flush(S);
+    sink_guard.armed = false;
     sink_close();
     scan_end(S);
     anchor_ranks_valid_ = want_anchor_ranks_;

@@ -222,6 +222,10 @@ public:
     // (bytes written, digest of those bytes in file order) of the last run's sink; the digest is kept when the sink is
     // "/dev/null" -- a test run whose rows nobody can keep -- or MMT_SINK_DIGEST is set
     void text_sink_digest(uint64_t out[2]) const { out[0] = sink_writer_.written(); out[1] = sink_writer_.digest(); }
+    // where the sink's helper thread and this thread spent their time in the last run that had a sink (the instrument of DESIGN.md
+    // section 7), and the host clock from the last piece leaving the device to the file having its name
+    const PieceWriter::Stats& text_sink_stats() const { return sink_writer_.stats(); }
+    double text_sink_tail_seconds() const { return sink_tail_s_; }
     void write_text_file(const std::string& path);
     // The row tap (tests/bigchecks.py check_bins_complete): every accepted interval of the NEXT runs whose match begins with
     // one of the given k-mers (k <= 16 characters each) leaves a copy of its length and all its suffix-array entries before
@@ -388,6 +392,8 @@ private:
     bool sink_force_discard_ = false, sink_keep_rows_ = false, sink_discard_ = false, sink_discarded_ = false;
     uint64_t sink_total_rows_ = 0;
     size_t sink_rows_done_ = 0;
+    static constexpr uint64_t SINK_TEXT_PER_BYTE = 12;                 // the sink's output is estimated at |T| / 12 bytes (sink_open)
+    double sink_tail_s_ = 0;
     PieceWriter sink_writer_;               // a ring of four page-locked blocks that stay with the engine between runs
     DevBuf<char> d_piece_[2];                // two pieces: one is copied out on the copy stream while the next is formatted
     hipStream_t sink_stream_ = nullptr;

@@ -33,6 +33,11 @@ struct StreamDigest {
 // The bytes go to PATH.tmp and take the final name in commit(): a run that fails half way -- a short write, a full disk, a
 // consistency check at its end -- must not leave a plausible but truncated PATH.  A path that exists and is not a regular
 // file (a FIFO, /dev/stdout) and "/dev/null" are written as they are; IN_PLACE writes any path under its own name.
+//
+// A PATH left by an earlier run is replaced by the rename -- and the file system frees its pages inside that call, the last
+// one before the run is over (~0.09 s per GB of a file in memory).  A writer that has idle time before its bytes arrive
+// calls retire_old() then: the old PATH goes at once, as with a tool that opens its output for writing when it starts,
+// and a run that fails afterwards leaves no PATH at all.
 class OutFile {
 public:
     enum Mode { RENAME, IN_PLACE };
@@ -44,17 +49,19 @@ public:
         struct stat sb;
         special_ = path == "/dev/null" || (::stat(path.c_str(), &sb) == 0 && !S_ISREG(sb.st_mode));
         rename_ = mode == RENAME && !special_;
-        path_ = path; name_ = rename_ ? path + ".tmp" : path; error_.clear();
+        path_ = path; name_ = rename_ ? path + ".tmp" : path; error_.clear(); written_ = 0;
         fd_ = ::open(name_.c_str(), special_ ? O_WRONLY : (O_CREAT | O_TRUNC | O_WRONLY), 0644);
         if (fd_ < 0) throw std::runtime_error("cannot write " + name_);
     }
+    // removes what an earlier run left under the final name (RENAME mode; nothing to do for the other files)
+    void retire_old() { if (rename_) ::unlink(path_.c_str()); }
     // false once a write has failed (the first failure stays in error(); later calls write nothing)
     bool write_all(const void* data, size_t n) {
         const char* src = static_cast<const char*>(data);
         for (size_t at = 0; error_.empty() && at < n;) {
             const ssize_t w = ::write(fd_, src + at, std::min<size_t>(n - at, (size_t)1 << 30));
             if (w <= 0) error_ = "short write to " + name_;
-            else at += (size_t)w;
+            else { at += (size_t)w; written_ += (uint64_t)w; }
         }
         return error_.empty();
     }
@@ -73,11 +80,13 @@ public:
     }
     bool special() const { return special_; }       // not a regular file: nobody can read the bytes back
     const std::string& error() const { return error_; }
+    uint64_t written() const { return written_; }
 
 private:
     std::string path_, name_, error_;
     int fd_ = -1;
     bool special_ = false, rename_ = false;
+    uint64_t written_ = 0;
 };
 
 }  // namespace mmt
