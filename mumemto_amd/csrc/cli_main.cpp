@@ -24,9 +24,11 @@
 #include <sys/wait.h>
 #include <unistd.h>
 
+#include "base_pack.hpp"
 #include "dist.hpp"
 #include "engine.hpp"
 #include "fasta.hpp"
+#include "kernels.hpp"
 #include "merge.hpp"
 #include "options.hpp"
 #include "out_file.hpp"
@@ -613,10 +615,18 @@ int main(int argc, char** argv) {
         std::thread engine_init;
         std::promise<void> engine_up;
         std::shared_future<void> engine_ready = engine_up.get_future().share();
+        // seconds since the process started: when the engine thread signalled engine_up, when the last reader finished
+        double engine_up_seconds = 0, readers_done_seconds = 0;
         // (a collection that will run as one suffix array through the parse proper peaks at ~10.5 bytes of device heap per text
         // character -- 123 GB mapped for the 12.03 G characters of the C3 stand-in --: the heap is mapped to that size while
         // the inputs are on their way, before any kernel runs.  Chunks mapped beside running work each waited ~30 ms for it:
         // 0.04 - 0.10 s of a 1.9 s process, and never the same twice.  MUMEMTO_NO_PREMAP switches it off.)
+        // (MUMEMTO_INPUT_CHUNK_MB: tuning aid; page-locked memory costs 0.19 s per GB when it is made and 0.13 s per GB at the exit)
+        const size_t CHUNK = (size_t)std::max(1, sw::num(sw::MUMEMTO_INPUT_CHUNK_MB, 8)) << 20;
+        // a chunk on its way (chunked input, below): CHUNK / 4 bytes of words, then the runs; one such buffer per reader
+        // thread on the device, behind the documents' slots, and two page-locked ones on the host
+        const size_t STAGE_WORDS = CHUNK / 4, DEV_STAGE = (STAGE_WORDS + BASE_PACK_RUN_CAP * sizeof(BaseRun) + 255) & ~(size_t)255;
+        const size_t stage_threads = reader_threads();
         size_t premap_bytes = 0, slots_bound = 0;
         if (!dry_run && !checkpoint && !sw::on(sw::MUMEMTO_NO_PREMAP)) {
             double file_bytes = 0;
@@ -625,7 +635,7 @@ int main(int argc, char** argv) {
                 // (9.9, 10.5 until round 6: the measured peak is 9.69 B per character -- 116.5 GB on the stand-in -- and what is mapped
                 // beyond the peak is memory the next process waits for while the driver scrubs it)
                 premap_bytes = (size_t)(9.9 * (o.use_rcomp ? 2.0 : 1.0) * file_bytes) + ((size_t)1 << 30);
-                slots_bound = (size_t)file_bytes + inputs.size() * 8192 + 4096;     // (the documents' slots: the readers must not wait for the mapping)
+                slots_bound = (size_t)file_bytes + inputs.size() * 8192 + 4096 + stage_threads * DEV_STAGE;     // (the documents' slots: the readers must not wait for the mapping)
             }
         }
         if (!dry_run)
@@ -633,6 +643,7 @@ int main(int argc, char** argv) {
                 try { engine.reset(new Engine(env_device(), nullptr)); }
                 catch (...) { engine_error = std::current_exception(); }
                 try { if (engine && slots_bound && slots_bound * 2 <= engine->auto_max_text()) (void)engine->begin_input_slots(slots_bound); } catch (...) {}
+                engine_up_seconds = secs_since(g_start);
                 engine_up.set_value();
                 if (engine && premap_bytes) pool::premap(engine->device(), premap_bytes);
             });
@@ -690,8 +701,10 @@ int main(int argc, char** argv) {
             up.thread.join();
         };
         struct UploadJoiner { std::function<void()> f; ~UploadJoiner() { f(); } } upload_joiner{finish_upload};
-        // Chunked input (fasta.hpp): a one-shot run never holds the collection in host memory -- every reader thread sends
-        // the bases it parses to the document's slot on the device through two page-locked 8 MB buffers of its own.  What
+        // Chunked input (fasta.hpp): a one-shot run never holds the collection in host memory -- every reader thread parses
+        // 8 MB of bases into an ordinary buffer of its own, packs them to two bits each (base_pack.hpp: a quarter of the bytes
+        // over the host link and a quarter of the page-locked memory) and has k::unpack_bases write them to the document's
+        // slot on the device, on one of four shared streams.  A chunk with more exception runs than the staging holds goes raw.  What
         // 6 GB of anonymous host memory cost this process: ~0.2 s of page faults while it was filled and 0.3 - 0.4 s between
         // _Exit and the parent's waitpid (tests/micro/exit_probe2.cpp; giving it back beside the run stalls the GPU's queues
         // for as long).  A run that turns out to need host copies (anchor partitions) reads the files again.
@@ -699,9 +712,16 @@ int main(int argc, char** argv) {
             std::vector<size_t> slot; size_t bytes = 0; bool on = false;
             std::atomic<bool> skipped{false};
             std::once_flag once; uint8_t* dev = nullptr; int device = 0;
+            // what went over the link, for the "input" object of MUMEMTO_STATS
+            std::atomic<uint64_t> chunks_packed{0}, chunks_raw{0}, bytes_sent{0}, exception_runs{0};
+            size_t stage_at = 0; std::atomic<size_t> threads{0};     // the readers' staging buffers on the device: behind the slots
+            // The readers share four streams (reader k: stream k % 4): the runtime makes streams one at a time, 5 - 6 ms each, so
+            // with a stream per reader the sixteenth began to send 0.1 s after the first; the process has four hardware queues
+            // anyway.  Every reader's staging is its own, and a stream keeps each reader's calls in the order it made them.
+            enum : size_t { STREAMS = 4 };
+            std::once_flag stream_once[STREAMS]; hipStream_t stream[STREAMS] = {nullptr, nullptr, nullptr, nullptr};
+            ~ChunkUp() { for (hipStream_t s : stream) if (s) (void)hipStreamDestroy(s); }
         } cu;
-        // (MUMEMTO_INPUT_CHUNK_MB: tuning aid; page-locked memory costs 0.19 s per GB when it is made and 0.13 s per GB at the exit)
-        const size_t CHUNK = (size_t)std::max(1, sw::num(sw::MUMEMTO_INPUT_CHUNK_MB, 8)) << 20;
         // (MUMEMTO_DRY_RUN_CHUNK=<bytes>, with MUMEMTO_DRY_RUN: the chunked reader into host vectors, chunks of that many bytes
         // -- the host-side test of the chunk logic, tests/test_cli_host.py)
         const size_t dry_chunk = dry_run && sw::is_set(sw::MUMEMTO_DRY_RUN_CHUNK) ? (size_t)std::max(1, sw::num(sw::MUMEMTO_DRY_RUN_CHUNK, 0)) : 0;
@@ -735,53 +755,98 @@ int main(int argc, char** argv) {
             t.chunk = CHUNK;
             t.swap = [&, i](uint8_t* filled, size_t n, uint64_t offset, bool more) -> uint8_t* {
                 if (cu.skipped.load()) return nullptr;
+                // (a reader thread gives its page-locked buffers back when it ends, i.e. when the inputs are read: what is
+                // still page-locked at the exit costs 0.13 s per GB there)
+                struct Bufs { std::unique_ptr<uint8_t[]> raw; uint8_t* stage[2] = {nullptr, nullptr}; uint8_t* raw_locked = nullptr;
+                              hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; bool busy[3] = {false, false, false};
+                              hipStream_t s = nullptr; uint8_t* dev_stage = nullptr; int next = 0;     // (ev[3]: the document's last call)
+                              ~Bufs() { for (uint8_t* b : {stage[0], stage[1], raw_locked}) if (b) (void)hipHostFree(b);
+                                        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); } };
+                static thread_local Bufs tb;
+                // the first chunk is parsed into ordinary memory before anybody asks whether the runtime is up
+                if (!tb.raw) tb.raw.reset(new uint8_t[CHUNK]);
+                if (!filled) return tb.raw.get();
                 std::call_once(cu.once, [&]() {
                     engine_ready.wait();
                     const uint64_t bound = 2 * ((uint64_t)cu.bytes + cu.slot.size());
                     if (engine_error || !engine || bound > engine->auto_max_text()) { cu.skipped.store(true); return; }
                     cu.device = engine->device();
-                    cu.dev = engine->begin_input_slots(cu.bytes);
+                    cu.stage_at = (cu.bytes + 64 + 255) & ~(size_t)255;
+                    cu.dev = engine->begin_input_slots(cu.stage_at + stage_threads * DEV_STAGE);
                 });
                 if (cu.skipped.load()) return nullptr;
-                // (a reader thread gives its page-locked buffers back when it ends, i.e. when the inputs are read: what is
-                // still page-locked at the exit costs 0.13 s per GB there)
-                struct Bufs { uint8_t* buf[2] = {nullptr, nullptr}; hipEvent_t ev[2] = {nullptr, nullptr}; bool busy[2] = {false, false};
-                              hipStream_t s = nullptr;
-                              ~Bufs() { for (int k = 0; k < 2; k++) { if (buf[k]) (void)hipHostFree(buf[k]); if (ev[k]) (void)hipEventDestroy(ev[k]); }
-                                        if (s) (void)hipStreamDestroy(s); } };
-                static thread_local Bufs tb;
                 if (!tb.s) {
+                    const size_t me = cu.threads++;
+                    if (me >= stage_threads) { cu.skipped.store(true); return nullptr; }   // (cannot happen: read_fasta_collection starts reader_threads() at most)
+                    tb.dev_stage = cu.dev + cu.stage_at + me * DEV_STAGE;
+                    const double t_begin = secs_since(g_start);
                     MMT_HIP(hipSetDevice(cu.device));
-                    MMT_HIP(hipStreamCreateWithFlags(&tb.s, hipStreamNonBlocking));
+                    std::call_once(cu.stream_once[me % cu.STREAMS], [&]() {
+                        MMT_HIP(hipStreamCreateWithFlags(&cu.stream[me % cu.STREAMS], hipStreamNonBlocking));
+                    });
+                    tb.s = cu.stream[me % cu.STREAMS];
+                    const double t_stream = secs_since(g_start);
+                    MMT_HIP(hipEventCreateWithFlags(&tb.ev[3], hipEventDisableTiming));
                     for (int k = 0; k < 2; k++) {
-                        MMT_HIP(hipHostMalloc(reinterpret_cast<void**>(&tb.buf[k]), CHUNK, hipHostMallocDefault));
+                        MMT_HIP(hipHostMalloc(reinterpret_cast<void**>(&tb.stage[k]), DEV_STAGE, hipHostMallocDefault));
                         MMT_HIP(hipEventCreateWithFlags(&tb.ev[k], hipEventDisableTiming));
                     }
+                    if (sw::on(sw::MUMEMTO_TIMING))
+                        std::fprintf(stderr, "[timing] reader %zu: first chunk parsed at %.3f, its stream at %.3f, its staging at %.3f\n", me,
+                                     t_begin, t_stream, secs_since(g_start));
                 }
-                const int k = filled == tb.buf[1] ? 1 : 0;
-                if (filled && n) {
-                    MMT_HIP(hipMemcpyAsync(cu.dev + cu.slot[i] + offset, filled, n, hipMemcpyHostToDevice, tb.s));
-                    MMT_HIP(hipEventRecord(tb.ev[k], tb.s));
-                    tb.busy[k] = true;
+                if (n) {
+                    // two bits a base into a page-locked staging buffer, words in front and runs behind them; the one on the
+                    // device is this reader's alone, and the stream's order keeps chunk j + 1 off it until chunk j is unpacked
+                    const int k = tb.next;
+                    if (tb.busy[k]) { MMT_HIP(hipEventSynchronize(tb.ev[k])); tb.busy[k] = false; }
+                    uint64_t* words = reinterpret_cast<uint64_t*>(tb.stage[k]);
+                    BaseRun* runs = reinterpret_cast<BaseRun*>(tb.stage[k] + STAGE_WORDS);
+                    const size_t n_runs = n <= CHUNK ? pack_bases(filled, n, words, runs, BASE_PACK_RUN_CAP) : BASE_PACK_OVERFLOW;
+                    uint8_t* dst = cu.dev + cu.slot[i] + offset;
+                    if (n_runs != BASE_PACK_OVERFLOW) {
+                        const size_t wb = base_pack_words(n) * sizeof(uint64_t), rb = n_runs * sizeof(BaseRun);
+                        MMT_HIP(hipMemcpyAsync(tb.dev_stage, words, wb, hipMemcpyHostToDevice, tb.s));
+                        if (rb) MMT_HIP(hipMemcpyAsync(tb.dev_stage + STAGE_WORDS, runs, rb, hipMemcpyHostToDevice, tb.s));
+                        MMT_HIP(hipEventRecord(tb.ev[k], tb.s));
+                        tb.busy[k] = true; tb.next = 1 - k;
+                        k::unpack_bases(reinterpret_cast<const uint64_t*>(tb.dev_stage), n,
+                                        reinterpret_cast<const BaseRun*>(tb.dev_stage + STAGE_WORDS), (uint32_t)n_runs, dst, tb.s);
+                        cu.chunks_packed++; cu.bytes_sent += wb + rb; cu.exception_runs += n_runs;
+                    } else {
+                        // more runs than the staging buffers hold: the chunk goes as it is, through a page-locked buffer made now
+                        if (!tb.raw_locked) {
+                            MMT_HIP(hipHostMalloc(reinterpret_cast<void**>(&tb.raw_locked), CHUNK, hipHostMallocDefault));
+                            MMT_HIP(hipEventCreateWithFlags(&tb.ev[2], hipEventDisableTiming));
+                        }
+                        if (tb.busy[2]) { MMT_HIP(hipEventSynchronize(tb.ev[2])); tb.busy[2] = false; }
+                        std::memcpy(tb.raw_locked, filled, n);
+                        MMT_HIP(hipMemcpyAsync(dst, tb.raw_locked, n, hipMemcpyHostToDevice, tb.s));
+                        MMT_HIP(hipEventRecord(tb.ev[2], tb.s));
+                        tb.busy[2] = true;
+                        cu.chunks_raw++; cu.bytes_sent += n;
+                    }
                 }
                 if (!more) {                        // the document is complete: on the device when this returns
-                    MMT_HIP(hipStreamSynchronize(tb.s));
-                    tb.busy[0] = tb.busy[1] = false;
+                    MMT_HIP(hipEventRecord(tb.ev[3], tb.s));        // (the stream is not this reader's alone: its own calls only)
+                    MMT_HIP(hipEventSynchronize(tb.ev[3]));
+                    tb.busy[0] = tb.busy[1] = tb.busy[2] = false;
                     return nullptr;
                 }
-                const int nk = filled ? 1 - k : 0;
-                if (tb.busy[nk]) { MMT_HIP(hipEventSynchronize(tb.ev[nk])); tb.busy[nk] = false; }
-                return tb.buf[nk];
+                return tb.raw.get();                // (packed or copied: free again)
             };
             return t;
         };
         if (!checkpoint) {
             long empty = read_fasta_collection(inputs, docs, arena, hd, &hooks);
-            if (empty == -2) {                      // the device turned out too small for one suffix array: host copies after all
+            // (the device turned out too small for one suffix array: host copies after all.  A reader learns that when it sends its
+            // first chunk; where that was a document's last one, nothing aborted the read and the flag alone says so)
+            if (empty == -2 || (cu.on && cu.skipped.load())) {
                 cu.on = false;
                 hooks.plan_chunks = nullptr; hooks.chunks = nullptr;
                 empty = read_fasta_collection(inputs, docs, arena, hd, &hooks);
             }
+            readers_done_seconds = secs_since(g_start);
             if (empty >= 0) {                       // ref_builder.cpp:249-252 + pfp_mum.cpp:68-71
                 std::cerr << std::endl << "Empty input file found: " << inputs[(size_t)empty] << std::endl;
                 throw CliError{"Please check the input files and ensure that it contains valid FASTA files. Cleaning up...", 1};
@@ -965,6 +1030,11 @@ int main(int argc, char** argv) {
         if (sw::on(sw::MUMEMTO_TIMING))
             std::fprintf(stderr, "[timing] device heap: %.2f GB live at the peak, %.2f GB mapped, %.3f s mapping it\n",
                          heap.peak / 1073741824.0, heap.mapped / 1073741824.0, heap.map_seconds);
+        if (sw::on(sw::MUMEMTO_TIMING))
+            std::fprintf(stderr, "[timing] input: chunks_packed %llu, chunks_raw %llu, bytes_sent %llu, exception_runs %llu, "
+                         "engine_up_seconds %.3f, readers_done_seconds %.3f\n", (unsigned long long)cu.chunks_packed.load(),
+                         (unsigned long long)cu.chunks_raw.load(), (unsigned long long)cu.bytes_sent.load(),
+                         (unsigned long long)cu.exception_runs.load(), engine_up_seconds, readers_done_seconds);
         if (const char* sp = sw::text(sw::MUMEMTO_STATS)) {       // one JSON object for bench.py
             const float* sm = eng.stage_ms();
             const float* pm = eng.pfp_state().ms;
@@ -987,6 +1057,10 @@ int main(int argc, char** argv) {
                << ", \"room_wait_written_ms\": " << ss.room_wait_s * 1e3 << ", \"room_wait_new_block_ms\": " << ss.room_create_s * 1e3
                << ", \"close_join_ms\": " << ss.join_s * 1e3 << ", \"close_commit_ms\": " << ss.commit_s * 1e3
                << ", \"tail_after_last_copy_ms\": " << eng.text_sink_tail_seconds() * 1e3 << "}";
+            // how the bases reached the device (chunked one-shot input), and when: seconds since the process started
+            js << ", \"input\": {\"chunks_packed\": " << cu.chunks_packed.load() << ", \"chunks_raw\": " << cu.chunks_raw.load()
+               << ", \"bytes_sent\": " << cu.bytes_sent.load() << ", \"exception_runs\": " << cu.exception_runs.load()
+               << ", \"engine_up_seconds\": " << engine_up_seconds << ", \"readers_done_seconds\": " << readers_done_seconds << "}";
             js << "}\n";
         }
         log_line("build_main", "Found " + std::to_string(R.n_rows) + " matches!");

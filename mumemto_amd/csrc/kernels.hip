@@ -318,6 +318,61 @@ void unpack_text(const TextRef& T, uint64_t first, uint64_t count, uint8_t* out,
     MMT_HIP(hipGetLastError());
 }
 
+// The bases of a FASTA chunk that crossed the host link at two bits each (base_pack.hpp) back as bytes, dst[0 .. n) and not a
+// byte beyond: the neighbouring bytes belong to other documents that other streams fill at the same moment.  dst has any
+// alignment (a document's slot starts wherever the file sizes put it), so the work is cut at dst's own 16-byte boundaries:
+// one work-item per aligned group of 16 bytes -- 32 bits of codes from one or two words, tx_expand8 twice, one 16-byte
+// store -- and the at most 15 bytes in front of the first group and behind the last one byte by byte.
+__global__ __launch_bounds__(256) void k_unpack_bases(const uint64_t* __restrict__ words, uint64_t n, uint8_t* __restrict__ dst,
+                                                       uint32_t head, uint64_t groups) {
+    const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g < groups) {
+        const uint64_t p = head + 16 * g;                        // first base of the group; p + 15 < n
+        const uint32_t sh = 2 * (uint32_t)(p & 31);
+        uint64_t bits = words[p >> 5] >> sh;
+        if (sh > 32) bits |= words[(p >> 5) + 1] << (64 - sh);   // (the group's last base lies in that word)
+        uint4 out;
+        const uint64_t lo = tx_expand8(bits), hi = tx_expand8(bits >> 16);
+        out.x = (uint32_t)lo; out.y = (uint32_t)(lo >> 32); out.z = (uint32_t)hi; out.w = (uint32_t)(hi >> 32);
+        *reinterpret_cast<uint4*>(dst + p) = out;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 32) {
+        const uint64_t tail_at = head + 16 * groups;
+        uint64_t p = n;
+        if (threadIdx.x < head) p = threadIdx.x;
+        else if (threadIdx.x >= 16 && tail_at + (threadIdx.x - 16) < n) p = tail_at + (threadIdx.x - 16);
+        if (p < n) dst[p] = (uint8_t)tx_expand8((words[p >> 5] >> (2 * (p & 31))) & 3u);
+    }
+}
+// The exception runs over them (a second launch on the same stream: it cannot race with the first).  Run r belongs to the
+// workgroups (r, 0 .. gridDim.y): each takes one segment of `seg` bytes of it, so a run of a megabase is several workgroups'
+// work and not one work-item's loop.  Runs are clipped to [0, n).
+__global__ __launch_bounds__(256) void k_unpack_runs(const BaseRun* __restrict__ runs, uint32_t n_runs, uint64_t n, uint64_t seg,
+                                                      uint8_t* __restrict__ dst) {
+    const uint32_t r = blockIdx.x;
+    if (r >= n_runs) return;
+    const uint64_t start = runs[r].start;
+    if (start >= n) return;
+    const uint64_t len = runs[r].len < n - start ? (uint64_t)runs[r].len : n - start;
+    const uint64_t from = (uint64_t)blockIdx.y * seg, upto = len < from + seg ? len : from + seg;
+    const uint8_t b = (uint8_t)runs[r].byte;
+    for (uint64_t j = from + threadIdx.x; j < upto; j += 256) dst[start + j] = b;
+}
+void unpack_bases(const uint64_t* words, uint64_t n, const BaseRun* runs, uint32_t n_runs, uint8_t* dst, hipStream_t s) {
+    if (!n) return;
+    const uint32_t head = (uint32_t)std::min<uint64_t>((16 - (reinterpret_cast<uintptr_t>(dst) & 15)) & 15, n);
+    const uint64_t groups = (n - head) / 16;
+    hipLaunchKernelGGL(k_unpack_bases, dim3(grid_for(groups, 256)), dim3(256), 0, s, words, n, dst, head, groups);
+    MMT_HIP(hipGetLastError());
+    if (!n_runs) return;
+    // (run r, segment y) per workgroup, up to sixteen segments a run while the launch stays below 2^24 workgroups (grid_for)
+    if (n_runs >= (1u << 23)) throw HipError("unpack_bases: 2^23 exception runs or more in one chunk");
+    const uint64_t parts = std::min<uint64_t>(16, (1u << 23) / n_runs);
+    const uint64_t seg = std::max<uint64_t>(4096, (n + parts - 1) / parts);
+    hipLaunchKernelGGL(k_unpack_runs, dim3(n_runs, (unsigned)((n + seg - 1) / seg)), dim3(256), 0, s, runs, n_runs, n, seg, dst);
+    MMT_HIP(hipGetLastError());
+}
+
 void build_text(const uint8_t* raw, const uint64_t* d_doc_base, const uint64_t* d_doc_len, const uint64_t* d_doc_start, uint32_t n_docs,
                 bool /*revcomp*/, uint8_t* text, uint64_t n, uint64_t* hist, hipStream_t s) {
     constexpr int B = 256;

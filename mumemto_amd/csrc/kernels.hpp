@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include "base_pack.hpp"
 #include "wide.hpp"
 #include "textref.hpp"
 
@@ -36,6 +37,9 @@ void pack_text(const uint8_t* raw, const uint64_t* d_doc_base, const uint64_t* d
 void pack_bytes(const uint8_t* text, uint64_t n, uint64_t* packed, uint64_t* ev_start, uint64_t* ev_end, uint32_t* ev_count,
                 uint32_t ev_cap, hipStream_t s);
 void unpack_text(const TextRef& T, uint64_t first, uint64_t count, uint8_t* out, hipStream_t s);
+// What pack_bases (base_pack.hpp) made of n bases, back as bytes: exactly dst[0 .. n) is written -- 'A' 'C' 'G' 'T' from the
+// codes, then the n_runs exception runs over them; dst has any alignment, words and runs are device memory.
+void unpack_bases(const uint64_t* words, uint64_t n, const BaseRun* runs, uint32_t n_runs, uint8_t* dst, hipStream_t s);
 
 // ---- A8 direct suffix sort (prefix doubling) --------------------------------
 // keys[i] = first `chars` symbols of suffix i, `bits` per symbol via code[256]
