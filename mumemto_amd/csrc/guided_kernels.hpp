@@ -67,6 +67,13 @@ struct Ctx {
     unsigned long long* prof = nullptr;
 };
 
+// the fields the dense tiles read, from the symbol code table (no_dense: the switch MMT_GUIDED_NO_DENSE); bits and chars are set
+inline void set_dense_codes(Ctx& c, const uint8_t code[256], bool no_dense) {
+    for (int k = 0; k < 4; k++) c.acgt[k] = code[(uint8_t)"ACGT"[k]];
+    c.acgt_lut = (uint32_t)c.acgt[0] | ((uint32_t)c.acgt[1] << 8) | ((uint32_t)c.acgt[2] << 16) | ((uint32_t)c.acgt[3] << 24);
+    c.dense_ok = c.acgt[0] && c.acgt[1] && c.acgt[2] && c.acgt[3] && c.chars <= 32 && !no_dense;
+}
+
 // A slice of a bin of ONE repeated symbol (guided_kernels.hip, "slices of a bin of one repeated symbol"): the suffixes c^r X of the
 // bin whose K = (X0 < c ? r : 2^41 - r) falls into the buckets [blo, bhi) -- a contiguous piece of the suffix array.  sym = 0: none.
 constexpr uint32_t RUN_BUCKETS_HALF = 8448;          // buckets per class: r exact below 256, then 256 per power of two up to 2^40

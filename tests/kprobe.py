@@ -1,6 +1,7 @@
 """ctypes / numpy side of tests/kprobe/libkprobe.so (single launch wrappers of the suffix sorter and of the prefix-free parse
 behind C functions), the plain references the sorter's kernel tests compare with, the generator of legal active lists, and
-(at the end) the texts, the packer and the thin wrappers of the parse's probes, whose references are tests/pfpmodel.py.
+(at the end) the texts, the packer and the thin wrappers of the parse's probes, whose references are tests/pfpmodel.py, and
+of the bucket-wise producer's (gk_*, with the context structure KpCtx), whose references are tests/guidedmodel.py.
 
 Everything in the references is integer arithmetic on numpy arrays or Python ints: there is no tolerance anywhere.
 The references import nothing from the product; tests/test_sorter_reference_host.py checks them (and the generator)
@@ -851,3 +852,344 @@ def parse_lcp(tx, nv, sa_p, pid, pstart, wide):
     sl = np.full(m, SENT32, U32); bmin = np.full(_rmq_alloc(m), SENT32, U32); dims = np.zeros(4, U32)
     call("parse_lcp", tx.arg(), c_u64(nv), u32(sa_p), u32(pid), _pos(pstart, wide), int(wide), m, sl, bmin, len(bmin), dims)
     return sl, bmin, int(dims[0]), int(dims[1]), int(dims[2]), int(dims[3])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the bucket-wise producer (csrc/guided_kernels.hpp, mmt::gk): gk_<wrapper> calls kp_gk_<wrapper>.  The references are
+# tests/guidedmodel.py.  Every in/out array is handed over as the caller made it (sentinels behind what may be written).
+# ---------------------------------------------------------------------------------------------------------------------
+SENT16 = 0xA5A5
+
+
+def sent(n, dtype):
+    """n sentinel entries of the type"""
+    return np.full(n, {1: SENT8, 2: SENT16, 4: SENT32, 8: SENT64}[np.dtype(dtype).itemsize], dtype)
+
+
+def gk_rank_counts(mask, n_counts, counts):
+    mask = u64(mask); call("gk_rank_counts", mask, c_u64(len(mask)), counts, c_u64(n_counts), len(counts))
+    return counts
+
+
+def gk_block_first_cut(mask, n_blocks, first):
+    mask = u64(mask); call("gk_block_first_cut", mask, c_u64(len(mask)), first, c_u64(n_blocks), len(first))
+    return first
+
+
+def gk_block_cut_counts(mask, n_blocks, counts):
+    mask = u64(mask); call("gk_block_cut_counts", mask, c_u64(len(mask)), counts, c_u64(n_blocks), len(counts))
+    return counts
+
+
+def gk_block_cut_offsets(mask, brank, n_blocks, coff):
+    mask = u64(mask); assert coff.dtype == np.uint16
+    call("gk_block_cut_offsets", mask, c_u64(len(mask)), u32(brank), coff, c_u64(n_blocks), len(coff))
+    return coff
+
+
+def gk_stage_block_tiles(tile_off, n, blk_tile):
+    tile_off = u32(tile_off); call("gk_stage_block_tiles", tile_off, len(tile_off), c_u64(n), blk_tile, len(blk_tile))
+    return blk_tile
+
+
+def gk_stage_count(staged, b0, b1, block_count):
+    staged = u32(staged); call("gk_stage_count", staged, c_u64(len(staged)), c_u32(b0), c_u32(b1), block_count, len(block_count))
+    return block_count
+
+
+def gk_heads0(keys, bits, chars, head, active, lcp):
+    keys = u64(keys); call("gk_heads0", keys, len(keys), head, active, lcp, len(head), bits, chars)
+    return head, active, lcp
+
+
+def gk_gather_active(idx, pos_sorted, head, slot, pos, headval):
+    idx = u32(idx); pos_sorted = u64(pos_sorted)
+    call("gk_gather_active", idx, len(idx), pos_sorted, u8(head), len(pos_sorted), slot, pos, headval, len(slot))
+    return slot, pos, headval
+
+
+def gk_medium_groups(ghead, cap, extra=3):
+    """(list as (4 * cap + extra, 2) words, count4 with one sentinel word behind it)"""
+    ghead = u32(ghead)
+    lst = sent((4 * cap + extra) * 2, U32).reshape(-1, 2); cnt = sent(5, U32)
+    call("gk_medium_groups", ghead, len(ghead), lst, cap, len(lst), cnt, len(cnt))
+    return lst, cnt
+
+
+def gk_tile_bounds(ghead, target, limit, n_tiles, bound):
+    ghead = u32(ghead); call("gk_tile_bounds", ghead, len(ghead), target, c_u32(limit), n_tiles, bound, len(bound))
+    return bound
+
+
+def gk_local_sort(kin, pin, ghead, bound, kout, pout, big_alloc, big_cap):
+    kin = u64(kin); m = len(kin)
+    bb = sent(big_alloc, U32); be = sent(big_alloc, U32); cnt = np.zeros(1, U32)
+    call("gk_local_sort", kin, u64(pin), u32(ghead), m, kout, pout, u32(bound), len(bound) - 1, bb, be, big_alloc, cnt, big_cap)
+    return kout, pout, bb, be, int(cnt[0])
+
+
+def gk_range_groups(ghead, big_begin, big_end, seg_alloc):
+    ghead = u32(ghead)
+    sb = sent(seg_alloc, U32); se = sent(seg_alloc, U32); cnt = sent(2, U32)
+    call("gk_range_groups", ghead, len(ghead), u32(big_begin), u32(big_end), len(big_begin), sb, se, seg_alloc, cnt, len(cnt))
+    return sb, se, cnt
+
+
+def gk_round_apply(pos_sorted, newhead, slot, out, flags):
+    newhead = u32(newhead)
+    call("gk_round_apply", u64(pos_sorted), newhead, u32(slot), len(newhead), out, len(out), flags, len(flags))
+    return out, flags
+
+
+def gk_round_compact(idx, slot, pos_sorted, newhead, slot_out, pos_out, headval_out):
+    idx = u32(idx); slot = u32(slot)
+    call("gk_round_compact", idx, len(idx), slot, u64(pos_sorted), u32(newhead), len(slot), slot_out, pos_out, headval_out, len(slot_out))
+    return slot_out, pos_out, headval_out
+
+
+def gk_flag_greater(v, thr, flags):
+    v = u32(v); call("gk_flag_greater", v, len(v), c_u32(thr), flags, len(flags))
+    return flags
+
+
+def gk_flag_spread(a, out):
+    a = u32(a); call("gk_flag_spread", a, len(a), out, len(out))
+    return out
+
+
+def gk_flag_to_distinct(occ_flag, pid, dflag):
+    pid = u32(pid); call("gk_flag_to_distinct", u32(occ_flag), pid, len(pid), dflag, len(dflag))
+    return dflag
+
+
+def gk_flag_from_distinct(dflag, pid, occ_flag):
+    dflag = u32(dflag); pid = u32(pid); call("gk_flag_from_distinct", dflag, len(dflag), pid, len(pid), occ_flag, len(occ_flag))
+    return occ_flag
+
+
+def gk_flag_scatter_ones(ids, flags):
+    ids = u32(ids); call("gk_flag_scatter_ones", ids, len(ids), flags, len(flags))
+    return flags
+
+
+def gk_giant_distinct(gids, rep, dlen, which, glen):
+    gids = u32(gids); rep = u32(rep)
+    call("gk_giant_distinct", gids, len(gids), rep, u32(dlen), len(rep), which, glen, len(which))
+    return which, glen
+
+
+def gk_giant_bits(flags, bits):
+    flags = u32(flags); call("gk_giant_bits", flags, len(flags), bits, len(bits))
+    return bits
+
+
+def gk_popcount_words(bits, out):
+    bits = u32(bits); call("gk_popcount_words", bits, len(bits), out, len(out))
+    return out
+
+
+def gk_giant_map(gids, gstart, dmap):
+    gids = u32(gids); call("gk_giant_map", gids, u32(gstart), len(gids), dmap, len(dmap))
+    return dmap
+
+
+def gk_giant_occurrences(gk, pid, pstart, wide, dmap, gps, gbase):
+    gk = u32(gk); pid = u32(pid); dmap = u32(dmap)
+    call("gk_giant_occurrences", gk, len(gk), pid, _pos(pstart, wide), int(wide), len(pid), dmap, len(dmap), gps, gbase, len(gps))
+    return gps, gbase
+
+
+def gk_giant_group_flags(esuf, lcp, flags):
+    esuf = u32(esuf); call("gk_giant_group_flags", esuf, u32(lcp), len(esuf), flags, len(flags))
+    return flags
+
+
+def gk_group_ids(ce_gs, gscan, B):
+    call("gk_group_ids", ce_gs, u32(gscan), B, len(ce_gs))
+    return ce_gs
+
+
+def gk_add_offset(table, n, add):
+    call("gk_add_offset", table, int(table.itemsize == 8), n, c_u64(add), len(table))
+    return table
+
+
+def gk_rep_bits(pid, rep, bits):
+    pid = u32(pid); rep = u32(rep); call("gk_rep_bits", pid, rep, len(rep), len(pid), bits, len(bits))
+    return bits
+
+
+class KpCtx(ctypes.Structure):
+    _fields_ = [("T", ctypes.c_void_p), ("n", ctypes.c_uint64), ("w", ctypes.c_uint32),
+                ("mask", ctypes.c_void_p), ("n_mask", ctypes.c_uint64), ("rdir", ctypes.c_void_p), ("n_rdir", ctypes.c_uint64),
+                ("nxt", ctypes.c_void_p), ("n_nxt", ctypes.c_uint64),
+                ("isa_p", ctypes.c_void_p), ("m", ctypes.c_uint32), ("code", ctypes.c_void_p), ("bits", ctypes.c_int), ("chars", ctypes.c_int),
+                ("skip", ctypes.c_uint32), ("pos_bits", ctypes.c_uint32), ("rec_rank", ctypes.c_uint32), ("no_dense", ctypes.c_uint32),
+                ("pid", ctypes.c_void_p), ("coff", ctypes.c_void_p), ("n_coff", ctypes.c_uint64), ("brank", ctypes.c_void_p), ("n_brank", ctypes.c_uint64),
+                ("g_k", ctypes.c_void_p), ("g_ps", ctypes.c_void_p), ("g_base", ctypes.c_void_p), ("g_n", ctypes.c_uint32),
+                ("g_isa", ctypes.c_void_p), ("g_grp", ctypes.c_void_p), ("g_lcp", ctypes.c_void_p), ("n_gisa", ctypes.c_uint32),
+                ("g_depth", ctypes.c_uint32), ("g_bits", ctypes.c_void_p), ("g_rank", ctypes.c_void_p), ("repbits", ctypes.c_void_p),
+                ("n_bitwords", ctypes.c_uint32), ("expand", ctypes.c_uint32)]
+
+
+class KpRunSlice(ctypes.Structure):
+    _fields_ = [("sym", ctypes.c_uint32), ("blo", ctypes.c_uint32), ("bhi", ctypes.c_uint32), ("lead", ctypes.c_void_p),
+                ("first", ctypes.c_void_p), ("follow", ctypes.c_void_p), ("n_tiles", ctypes.c_uint64)]
+
+
+class GkCtx:
+    """gk::Ctx for the probe from a model context (tests/guidedmodel.py Ctx): the text in `text_layout` ("bytes" / "packed"),
+    the phrase ends as "bits" (mask, rdir) or as "list" (coff, brank).  Keeps every array alive."""
+
+    def __init__(self, c, text_layout="bytes", cuts="bits", no_dense=0):
+        self.tx = Text(c.text, text_layout)
+        t = c.t
+        self.keep = {"nxt": u64(t.nxt), "code": u8(c.code)}
+        if cuts == "bits":
+            self.keep.update(mask=u64(t.mask), rdir=u32(np.concatenate([t.rdir, [0]])))
+        else:
+            assert cuts == "list"
+            self.keep.update(coff=np.ascontiguousarray(t.coff, dtype=np.uint16), brank=u32(t.brank))
+        for name in ("isa_p", "pid"):
+            if getattr(c, name) is not None:
+                self.keep[name] = u32(getattr(c, name))
+        if c.rep is not None:
+            self.keep["repbits"] = c.bitwords(c.rep)
+        g = c.giant
+        if g is not None:
+            bits = c.bitwords(g.flag)
+            self.keep.update(g_k=u32(g.k), g_ps=u64(g.ps), g_base=u32(g.base), g_isa=u32(g.isa), g_grp=u32(g.grp), g_lcp=u32(g.lcp),
+                             g_bits=bits, g_rank=g.rank_words(bits))
+        k = self.k = KpCtx()
+        k.T = ctypes.addressof(self.tx.c); k.n = c.n; k.w = c.w; k.m = c.m; k.bits = c.bits; k.chars = c.chars
+        k.skip = c.skip; k.pos_bits = c.pos_bits; k.rec_rank = c.rec_rank; k.no_dense = no_dense; k.expand = c.expand
+        k.g_depth = c.g_depth; k.g_n = 0 if g is None else len(g.k); k.n_gisa = 0 if g is None else len(g.isa)
+        k.n_bitwords = c.m // 32 + 1
+        for name, a in self.keep.items():
+            setattr(k, name, a.ctypes.data)
+            if hasattr(k, "n_" + name):
+                setattr(k, "n_" + name, len(a))
+
+    def arg(self):
+        return ctypes.byref(self.k)
+
+
+def run_slice_arg(rs):
+    """(ctypes argument, what keeps it alive) of a model RunSlice, or (NULL, None)"""
+    if rs is None:
+        return None, None
+    keep = (u64(rs.lead), u8(rs.first), u8(rs.follow))
+    r = KpRunSlice(rs.sym, rs.blo, rs.bhi, keep[0].ctypes.data, keep[1].ctypes.data, keep[2].ctypes.data, len(keep[0]))
+    return ctypes.byref(r), (r, keep)
+
+
+def gk_tile_lead(g, first, lead, follow):
+    call("gk_tile_lead", g.arg(), first, lead, follow, len(first))
+    return first, lead, follow
+
+
+def gk_run_hist(g, pc, bin_, rs, hist):
+    a, keep = run_slice_arg(rs)
+    call("gk_run_hist", g.arg(), pc, c_u32(bin_), a, hist, len(hist))
+    return hist
+
+
+def gk_bin_hist(g, pc, hist):
+    call("gk_bin_hist", g.arg(), pc, hist, len(hist))
+    return hist
+
+
+def gk_batch_count(g, pc, lo, hi, tile_count, rs=None):
+    a, keep = run_slice_arg(rs)
+    call("gk_batch_count", g.arg(), pc, c_u32(lo), c_u32(hi), a, tile_count, len(tile_count))
+    return tile_count
+
+
+def gk_batch_fill(g, pc, lo, hi, tile_off, keys, pos, next_lo, next_hi, next_count, rs=None):
+    a, keep = run_slice_arg(rs)
+    call("gk_batch_fill", g.arg(), pc, c_u32(lo), c_u32(hi), u32(tile_off), keys, pos, len(keys), c_u32(next_lo), c_u32(next_hi),
+         next_count, 0 if next_count is None else len(next_count), a)
+    return keys, pos, next_count
+
+
+def gk_stage_fill(g, pc, lo, hi, tile_off, staged, next_lo, next_hi, next_count):
+    call("gk_stage_fill", g.arg(), pc, c_u32(lo), c_u32(hi), u32(tile_off), staged, len(staged), c_u32(next_lo), c_u32(next_hi),
+         next_count, 0 if next_count is None else len(next_count))
+    return staged, next_count
+
+
+def gk_stage_take(g, staged, b0, b1, block_off, keys, pos, nb0, nb1, next_count, tile_off, blk_tile):
+    staged = u32(staged)
+    call("gk_stage_take", g.arg(), staged, c_u64(len(staged)), c_u32(b0), c_u32(b1), u32(block_off), keys, pos, len(keys), c_u32(nb0),
+         c_u32(nb1), next_count, 0 if next_count is None else len(next_count), u32(tile_off), u32(blk_tile))
+    return keys, pos, next_count
+
+
+def gk_phrase_items(g, pstart, wide, rep, keys, pos):
+    pstart = _pos(pstart, wide); rep = u32(rep)
+    call("gk_phrase_items", g.arg(), pstart, int(wide), len(pstart), rep, len(rep), keys, pos, len(keys))
+    return keys, pos
+
+
+def gk_round_keys(g, pos, offset, keys, err, gr=None, pure=None, ghead=None):
+    pos = u64(pos)
+    call("gk_round_keys", g.arg(), pos, len(pos), c_u64(offset), keys, len(keys), err, None if gr is None else u32(gr),
+         None if pure is None else u8(pure), None if ghead is None else u32(ghead))
+    return keys, err
+
+
+def gk_giant_probe(g, pos, ghead, offset, gr, pure):
+    pos = u64(pos)
+    call("gk_giant_probe", g.arg(), pos, u32(ghead), len(pos), c_u64(offset), gr, pure, len(gr))
+    return gr, pure
+
+
+def gk_round_heads(g, keys, ghead, headval, err, lcp_out=None, slot=None, offset=0, pure=None):
+    keys = u64(keys)
+    call("gk_round_heads", g.arg(), keys, u32(ghead), len(keys), headval, len(headval), err, lcp_out,
+         0 if lcp_out is None else len(lcp_out), None if slot is None else u32(slot), c_u64(offset), None if pure is None else u8(pure))
+    return headval, err, lcp_out
+
+
+def gk_write_columns(g, pos, base, sa_lo, sa_hi, bwt):
+    pos = u64(pos)
+    call("gk_write_columns", g.arg(), pos, len(pos), c_u64(base), sa_lo, sa_hi, bwt, len(sa_lo))
+    return sa_lo, sa_hi, bwt
+
+
+def gk_phrase_ranks(g, pos, pid, prank):
+    pos = u64(pos)
+    call("gk_phrase_ranks", g.arg(), pos, len(pos), u32(pid), prank, len(prank))
+    return prank
+
+
+def gk_expand_entries(g, pos, lcp, tab, cols, err):
+    pos = u64(pos); tab = u32(tab).reshape(-1, 4)
+    call("gk_expand_entries", g.arg(), pos, u32(lcp), len(pos), tab, len(tab), cols["cnt"], cols["first"], cols["offm1"], cols["bwt"],
+         cols["gs"], cols["hl"], cols["slen"], len(cols["cnt"]), err)
+    return cols, err
+
+
+def gk_resolve_small(g, pos, ghead, slot, offset, out, flags, err, lcp_out=None, limit=0):
+    pos = u64(pos)
+    call("gk_resolve_small", g.arg(), pos, u32(ghead), u32(slot), len(pos), c_u64(offset), out, len(out), flags, len(flags), err, lcp_out, limit)
+    return out, flags, err, lcp_out
+
+
+def gk_batch_lcp(g, sl, pos, carry, lcp, err):
+    pos = u64(pos); sl = u32(sl)
+    call("gk_batch_lcp", g.arg(), sl, len(sl), pos, len(pos), None if carry is None else u64(carry), lcp, len(lcp), err)
+    return lcp, err
+
+
+def gk_resolve_medium(g, sl, pos, slot, classes, cap, offset, out, flags, err, lcp_out=None):
+    """classes: four lists of (first, size); laid out as the four regions of `cap` pairs"""
+    pos = u64(pos); sl = u32(sl)
+    lst = sent(8 * cap, U32).reshape(4, cap, 2)
+    for cl, groups in enumerate(classes):
+        for i, (first, size) in enumerate(groups):
+            lst[cl, i] = (first, size)
+    n_groups = u32([len(x) for x in classes])
+    call("gk_resolve_medium", g.arg(), sl, len(sl), pos, len(pos), u32(slot), lst, cap, n_groups, c_u64(offset), out, len(out), flags,
+         len(flags), lcp_out, err)
+    return out, flags, err, lcp_out

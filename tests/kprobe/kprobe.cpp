@@ -1,6 +1,7 @@
 // kprobe.cpp -- test infrastructure: plain C entry points around single launch wrappers of the suffix sorter
-// (mmt::k, mmt::prims, pk::pack_keys_u32, DoublingSorter::sort) and of the prefix-free parse (mmt::pk rows A2-A4, the
-// dictionary's LCP steps of mmt::k, build_rmq / ParseLcp::build / rmq_min of parse_lcp.hpp), for tests/kprobe.py.
+// (mmt::k, mmt::prims, pk::pack_keys_u32, DoublingSorter::sort), of the prefix-free parse (mmt::pk rows A2-A4, the
+// dictionary's LCP steps of mmt::k, build_rmq / ParseLcp::build / rmq_min of parse_lcp.hpp) and of the bucket-wise producer
+// (mmt::gk, guided_kernels.hpp: the kp_gk_* functions at the end), for tests/kprobe.py.
 //
 // Every kp_* function takes host arrays, uploads them, calls exactly ONE wrapper, synchronises and copies the results
 // back; arrays marked "in/out" go up as the caller filled them (sentinel patterns: what the wrapper must not touch
@@ -14,10 +15,12 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include <hip/hip_runtime.h>
 
 #include "device_utils.hpp"
+#include "guided_kernels.hpp"
 #include "kernels.hpp"
 #include "parse_lcp.hpp"
 #include "pfp_kernels.hpp"
@@ -875,5 +878,748 @@ KP int kp_parse_lcp(const KpText* tx, u64 nv, const u32* sa_p, const u32* pid, c
         MMT_HIP(hipMemcpyAsync(sl, L.sl.get(), (size_t)m * 4, hipMemcpyDeviceToHost, stream()));
         MMT_HIP(hipMemcpyAsync(bmin, L.bmin.get(), (size_t)L.nb * L.levels * 4, hipMemcpyDeviceToHost, stream()));
         dims[0] = L.nb; dims[1] = L.levels; dims[2] = L.n_irreducible; dims[3] = L.n_long;
+    });
+}
+
+// ==== guided_kernels.hpp (mmt::gk): the bucket-wise producer's wrappers, kp_gk_<wrapper> ================================
+// The model of these kernels is tests/guidedmodel.py, their cases tests/guided_cases.py (which mirrors the need(...) lines
+// below, so that the CPU suite knows that no designed case is rejected here).
+static u32 popc64(u64 x) { return (u32)__builtin_popcountll(x); }
+// ---- phrase-end tables ------------------------------------------------------------------------------------------------
+// counts (alloc entries): in/out
+KP int kp_gk_rank_counts(const u64* mask, u64 n_words, u32* counts, u64 n_counts, u32 alloc) {
+    return guarded([&] {
+        need(alloc >= n_counts, "counts holds n_counts entries");
+        Dev<u64> m(mask, n_words);
+        Dev<u32> c(counts, alloc);
+        gk::rank_counts(m.p(), n_words, c.p(), n_counts, stream());
+        c.down(counts);
+    });
+}
+KP int kp_gk_block_first_cut(const u64* mask, u64 n_words, u64* first, u64 n_blocks, u32 alloc) {      // first: in/out
+    return guarded([&] {
+        need(alloc >= n_blocks, "first holds n_blocks entries");
+        Dev<u64> m(mask, n_words), f(first, alloc);
+        gk::block_first_cut(m.p(), n_words, f.p(), n_blocks, stream());
+        f.down(first);
+    });
+}
+KP int kp_gk_block_cut_counts(const u64* mask, u64 n_words, u32* counts, u64 n_blocks, u32 alloc) {    // counts: in/out
+    return guarded([&] {
+        need(alloc >= n_blocks, "counts holds n_blocks entries");
+        Dev<u64> m(mask, n_words);
+        Dev<u32> c(counts, alloc);
+        gk::block_cut_counts(m.p(), n_words, c.p(), n_blocks, stream());
+        c.down(counts);
+    });
+}
+// brank: n_blocks entries; coff (alloc entries): in/out
+KP int kp_gk_block_cut_offsets(const u64* mask, u64 n_words, const u32* brank, uint16_t* coff, u64 n_blocks, u32 alloc) {
+    return guarded([&] {
+        for (u64 b = 0; b < n_blocks; b++) {
+            u64 c = 0;
+            for (u64 wi = b * 64; wi < std::min<u64>(n_words, (b + 1) * 64); wi++) c += popc64(mask[wi]);
+            need((u64)brank[b] + c <= alloc, "brank + the block's cuts beyond coff");
+        }
+        Dev<u64> m(mask, n_words);
+        Dev<u32> br(brank, n_blocks);
+        Dev<uint16_t> co(coff, alloc);
+        gk::block_cut_offsets(m.p(), n_words, br.p(), co.p(), n_blocks, stream());
+        co.down(coff);
+    });
+}
+
+// ---- staged lists (the context-free half) -------------------------------------------------------------------------------
+// tile_off: n_tiles entries; blk_tile (alloc entries): in/out
+KP int kp_gk_stage_block_tiles(const u32* tile_off, u32 n_tiles, u64 n, u32* blk_tile, u32 alloc) {
+    return guarded([&] {
+        need(n_tiles >= 1 && n < (1ull << 32), "n_tiles >= 1, a list below 2^32 entries");
+        need(n == 0 || alloc >= (n + 4095) / 4096 + 1, "blk_tile holds blocks + 1 entries");
+        Dev<u32> to(tile_off, n_tiles), bt(blk_tile, alloc);
+        gk::stage_block_tiles(to.p(), n_tiles, n, bt.p(), stream());
+        bt.down(blk_tile);
+    });
+}
+KP int kp_gk_stage_count(const u32* staged, u64 n, u32 b0, u32 b1, u32* block_count, u32 alloc) {     // block_count: in/out
+    return guarded([&] {
+        need(alloc >= (n + 4095) / 4096, "block_count holds one entry per 4096 entries");
+        Dev<u32> st(staged, n), bc(block_count, alloc);
+        gk::stage_count(st.p(), n, b0, b1, bc.p(), stream());
+        bc.down(block_count);
+    });
+}
+
+// ---- first keys and rounds ------------------------------------------------------------------------------------------
+// head, active (alloc entries), lcp (alloc entries, or null): in/out
+KP int kp_gk_heads0(const u64* keys, u32 B, u8* head, u8* active, u32* lcp, u32 alloc, int bits, int chars) {
+    return guarded([&] {
+        need(alloc >= B && bits >= 1 && chars >= 1 && bits * chars <= 64, "B entries, 1 <= bits * chars <= 64");
+        Dev<u64> k(keys, B);
+        Dev<u8> h(head, alloc), a(active, alloc);
+        Dev<u32> l(lcp, lcp ? alloc : 0);
+        gk::heads0(k.p(), B, h.p(), a.p(), lcp ? l.p() : nullptr, bits, chars, stream());
+        h.down(head); a.down(active); l.down(lcp);
+    });
+}
+// pos_sorted, head: B entries; slot, pos, headval (alloc entries): in/out
+KP int kp_gk_gather_active(const u32* idx, u32 m, const u64* pos_sorted, const u8* head, u32 B, u32* slot, u64* pos, u32* headval,
+                           u32 alloc) {
+    return guarded([&] {
+        need(alloc >= m, "the outputs hold m entries");
+        for (u32 c = 0; c < m; c++) need(idx[c] < B, "idx beyond the batch");
+        Dev<u32> i(idx, m), sl(slot, alloc), hv(headval, alloc);
+        Dev<u64> ps(pos_sorted, B), po(pos, alloc);
+        Dev<u8> h(head, B);
+        gk::gather_active(i.p(), m, ps.p(), h.p(), sl.p(), po.p(), hv.p(), stream());
+        sl.down(slot); po.down(pos); hv.down(headval);
+    });
+}
+// group heads of a list of m elements: ghead[c] = index of the first element of c's group
+static void check_gheads(const u32* ghead, u32 m) {
+    for (u32 c = 0; c < m; c++) need(ghead[c] == c || (c > 0 && ghead[c] == ghead[c - 1] && ghead[c] < c), "ghead: every element names the first of its group");
+}
+// list (2 * alloc words: pairs, 4 regions of cap), count4 (count_alloc >= 4 words): in/out
+KP int kp_gk_medium_groups(const u32* ghead, u32 m, u32* list, u32 cap, u32 alloc, u32* count4, u32 count_alloc) {
+    return guarded([&] {
+        check_gheads(ghead, m);
+        need(count_alloc >= 4 && alloc >= 4 * (u64)cap, "count4 holds 4 words, list 4 regions of cap pairs");
+        u32 cnt[4] = {0, 0, 0, 0};
+        for (u32 e = 0; e < m; e++)
+            if (e + 1 == m || ghead[e + 1] != ghead[e]) {
+                const u32 sz = e - ghead[e] + 1;
+                if (sz <= 128) cnt[sz <= 16 ? 0 : (sz <= 32 ? 1 : (sz <= 64 ? 2 : 3))]++;
+            }
+        for (int cl = 0; cl < 4; cl++) need(cnt[cl] <= cap, "a class has more groups than a region holds");
+        Dev<u32> g(ghead, m), l(list, 2 * (size_t)alloc), c4(count4, count_alloc);
+        gk::medium_groups(g.p(), m, l.p(), cap, c4.p(), stream());
+        l.down(list); c4.down(count4);
+    });
+}
+KP int kp_gk_tile_bounds(const u32* ghead, u32 m, u32 target, u32 limit, u32 n_tiles, u32* bound, u32 alloc) {    // bound: in/out
+    return guarded([&] {
+        need(alloc >= (u64)n_tiles + 1 && target >= 1, "bound holds n_tiles + 1 entries");
+        Dev<u32> g(ghead, m), b(bound, alloc);
+        gk::tile_bounds(g.p(), m, target, limit, n_tiles, b.p(), stream());
+        b.down(bound);
+    });
+}
+// kout, pout (m entries), big_begin, big_end (big_alloc entries), big_count: in/out
+KP int kp_gk_local_sort(const u64* kin, const u64* pin, const u32* ghead, u32 m, u64* kout, u64* pout, const u32* bound, u32 n_tiles,
+                        u32* big_begin, u32* big_end, u32 big_alloc, u32* big_count, u32 big_cap) {
+    return guarded([&] {
+        need(big_cap <= big_alloc && n_tiles >= 1, "big_cap within the lists, a tile at least");
+        check_gheads(ghead, m);
+        need(bound[n_tiles] != gk::NO_BOUND, "the last bound ends every search");
+        for (u32 t = 0; t <= n_tiles; t++)
+            need(bound[t] == gk::NO_BOUND || (bound[t] <= m && (bound[t] == m || ghead[bound[t]] == bound[t])), "a bound is a group's head or m");
+        Dev<u64> ki(kin, m), pi(pin, m), ko(kout, m), po(pout, m);
+        Dev<u32> g(ghead, m), b(bound, (size_t)n_tiles + 1), bb(big_begin, big_alloc), be(big_end, big_alloc), bc(big_count, 1);
+        gk::local_sort(ki.p(), pi.p(), g.p(), ko.p(), po.p(), b.p(), n_tiles, bb.p(), be.p(), bc.p(), big_cap, stream());
+        ko.down(kout); po.down(pout); bb.down(big_begin); be.down(big_end); bc.down(big_count);
+    });
+}
+// seg_begin, seg_end (seg_alloc entries), seg_count (count_alloc >= 1 entries): in/out
+KP int kp_gk_range_groups(const u32* ghead, u32 m, const u32* big_begin, const u32* big_end, u32 big, u32* seg_begin, u32* seg_end,
+                          u32 seg_alloc, u32* seg_count, u32 count_alloc) {
+    return guarded([&] {
+        need(big >= 1 && count_alloc >= 1, "a range at least");
+        check_gheads(ghead, m);
+        u64 segs = 0;
+        for (u32 r = 0; r < big; r++) {
+            need(big_begin[r] <= big_end[r] && big_end[r] <= m, "a range within the list");
+            for (u32 c = big_begin[r]; c < big_end[r]; c++) segs += (c + 1 == big_end[r] || ghead[c + 1] == c + 1) ? 1 : 0;
+        }
+        need(segs <= seg_alloc, "more groups than the segment lists hold");
+        Dev<u32> g(ghead, m), bb(big_begin, big), be(big_end, big), sb(seg_begin, seg_alloc), se(seg_end, seg_alloc), sc(seg_count, count_alloc);
+        gk::range_groups(g.p(), bb.p(), be.p(), big, sb.p(), se.p(), sc.p(), stream());
+        sb.down(seg_begin); se.down(seg_end); sc.down(seg_count);
+    });
+}
+// out (out_alloc entries), flags (alloc entries): in/out
+KP int kp_gk_round_apply(const u64* pos_sorted, const u32* newhead, const u32* slot, u32 m, u64* out, u32 out_alloc, u8* flags, u32 alloc) {
+    return guarded([&] {
+        need(alloc >= m, "flags holds m entries");
+        for (u32 c = 0; c < m; c++) need(slot[c] < out_alloc, "slot beyond out");
+        Dev<u64> ps(pos_sorted, m), o(out, out_alloc);
+        Dev<u32> nh(newhead, m), sl(slot, m);
+        Dev<u8> f(flags, alloc);
+        gk::round_apply(ps.p(), nh.p(), sl.p(), m, o.p(), f.p(), stream());
+        o.down(out); f.down(flags);
+    });
+}
+// slot, pos_sorted, newhead: m entries; the outputs (alloc entries): in/out
+KP int kp_gk_round_compact(const u32* idx, u32 m2, const u32* slot, const u64* pos_sorted, const u32* newhead, u32 m, u32* slot_out,
+                           u64* pos_out, u32* headval_out, u32 alloc) {
+    return guarded([&] {
+        need(alloc >= m2, "the outputs hold m2 entries");
+        for (u32 c = 0; c < m2; c++) need(idx[c] < m, "idx beyond the round's list");
+        Dev<u32> i(idx, m2), sl(slot, m), nh(newhead, m), so(slot_out, alloc), ho(headval_out, alloc);
+        Dev<u64> ps(pos_sorted, m), po(pos_out, alloc);
+        gk::round_compact(i.p(), m2, sl.p(), ps.p(), nh.p(), so.p(), po.p(), ho.p(), stream());
+        so.down(slot_out); po.down(pos_out); ho.down(headval_out);
+    });
+}
+
+// ---- giant bookkeeping ------------------------------------------------------------------------------------------------
+KP int kp_gk_flag_greater(const u32* v, u32 n, u32 thr, u32* flags, u32 alloc) {              // flags: in/out
+    return guarded([&] {
+        need(alloc >= n, "flags holds n entries");
+        Dev<u32> a(v, n), f(flags, alloc);
+        gk::flag_greater(a.p(), n, thr, f.p(), stream());
+        f.down(flags);
+    });
+}
+KP int kp_gk_flag_spread(const u32* in, u32 n, u32* out, u32 alloc) {                         // out: in/out
+    return guarded([&] {
+        need(alloc >= n, "out holds n entries");
+        Dev<u32> a(in, n), o(out, alloc);
+        gk::flag_spread(a.p(), n, o.p(), stream());
+        o.down(out);
+    });
+}
+KP int kp_gk_flag_to_distinct(const u32* occ_flag, const u32* pid, u32 m, u32* dflag, u32 alloc) {   // dflag: in/out
+    return guarded([&] {
+        for (u32 k = 0; k < m; k++) need(pid[k] < alloc, "pid beyond dflag");
+        Dev<u32> of(occ_flag, m), pi(pid, m), d(dflag, alloc);
+        gk::flag_to_distinct(of.p(), pi.p(), m, d.p(), stream());
+        d.down(dflag);
+    });
+}
+KP int kp_gk_flag_from_distinct(const u32* dflag, u32 D, const u32* pid, u32 m, u32* occ_flag, u32 alloc) {   // occ_flag: in/out
+    return guarded([&] {
+        need(alloc >= m, "occ_flag holds m entries");
+        for (u32 k = 0; k < m; k++) need(pid[k] < D, "pid beyond dflag");
+        Dev<u32> d(dflag, D), pi(pid, m), of(occ_flag, alloc);
+        gk::flag_from_distinct(d.p(), pi.p(), m, of.p(), stream());
+        of.down(occ_flag);
+    });
+}
+KP int kp_gk_flag_scatter_ones(const u32* ids, u32 n, u32* flags, u32 alloc) {                // flags: in/out
+    return guarded([&] {
+        for (u32 i = 0; i < n; i++) need(ids[i] < alloc, "ids beyond flags");
+        Dev<u32> a(ids, n), f(flags, alloc);
+        gk::flag_scatter_ones(a.p(), n, f.p(), stream());
+        f.down(flags);
+    });
+}
+KP int kp_gk_giant_distinct(const u32* gids, u32 n, const u32* rep, const u32* dlen, u32 D, u32* which, u32* glen, u32 alloc) {
+    return guarded([&] {
+        need(alloc >= n, "which / glen hold n entries");
+        for (u32 i = 0; i < n; i++) need(gids[i] < D, "gids beyond rep / dlen");
+        Dev<u32> g(gids, n), r(rep, D), dl(dlen, D), wh(which, alloc), gl(glen, alloc);
+        gk::giant_distinct(g.p(), n, r.p(), dl.p(), wh.p(), gl.p(), stream());
+        wh.down(which); gl.down(glen);
+    });
+}
+KP int kp_gk_giant_bits(const u32* flags, u32 m, u32* bits, u32 alloc) {                      // bits: in/out
+    return guarded([&] {
+        need(alloc >= ((u64)m + 31) / 32, "bits holds a word per 32 flags");
+        Dev<u32> f(flags, m), b(bits, alloc);
+        gk::giant_bits(f.p(), m, b.p(), stream());
+        b.down(bits);
+    });
+}
+KP int kp_gk_popcount_words(const u32* bits, u32 n, u32* out, u32 alloc) {                    // out: in/out
+    return guarded([&] {
+        need(alloc >= n, "out holds n entries");
+        Dev<u32> b(bits, n), o(out, alloc);
+        gk::popcount_words(b.p(), n, o.p(), stream());
+        o.down(out);
+    });
+}
+KP int kp_gk_giant_map(const u32* gids, const u32* gstart, u32 n, u32* dmap, u32 alloc) {     // dmap: in/out
+    return guarded([&] {
+        for (u32 i = 0; i < n; i++) need(gids[i] < alloc, "gids beyond dmap");
+        Dev<u32> g(gids, n), gs(gstart, n), d(dmap, alloc);
+        gk::giant_map(g.p(), gs.p(), n, d.p(), stream());
+        d.down(dmap);
+    });
+}
+// pid, pstart: m entries; gps, gbase (alloc entries): in/out
+KP int kp_gk_giant_occurrences(const u32* gk_, u32 n, const u32* pid, const void* pstart, int wide, u32 m, const u32* dmap, u32 D,
+                               u64* gps, u32* gbase, u32 alloc) {
+    return guarded([&] {
+        need(alloc >= n, "gps / gbase hold n entries");
+        for (u32 j = 0; j < n; j++) need(gk_[j] < m && pid[gk_[j]] < D, "gk beyond the parse, or pid beyond dmap");
+        Dev<u32> g(gk_, n), pi(pid, m), dm(dmap, D), gb(gbase, alloc);
+        DevPos ps(pstart, m, wide != 0);
+        Dev<u64> gp(gps, alloc);
+        gk::giant_occurrences(g.p(), n, pi.p(), ps.p(), wide != 0, dm.p(), gp.p(), gb.p(), stream());
+        gp.down(gps); gb.down(gbase);
+    });
+}
+KP int kp_gk_giant_group_flags(const u32* esuf, const u32* lcp, u32 nd, u32* flags, u32 alloc) {   // flags: in/out
+    return guarded([&] {
+        need(alloc >= nd, "flags holds nd entries");
+        Dev<u32> es(esuf, nd), l(lcp, nd), f(flags, alloc);
+        gk::giant_group_flags(es.p(), l.p(), nd, f.p(), stream());
+        f.down(flags);
+    });
+}
+
+// ---- results (the context-free half) ------------------------------------------------------------------------------------
+KP int kp_gk_group_ids(u32* ce_gs, const u32* gscan, u32 B, u32 alloc) {                      // ce_gs: in/out
+    return guarded([&] {
+        need(alloc >= B, "ce_gs holds B entries");
+        Dev<u32> g(ce_gs, alloc), sc(gscan, B);
+        gk::group_ids(g.p(), sc.p(), B, stream());
+        g.down(ce_gs);
+    });
+}
+KP int kp_gk_add_offset(void* table, int wide, u32 n, u64 add, u32 alloc) {                   // table: in/out
+    return guarded([&] {
+        need(alloc >= n, "table holds n entries");
+        DevPos t(table, alloc, wide != 0);
+        gk::add_offset(t.p(), wide != 0, n, add, stream());
+        t.down(table);
+    });
+}
+KP int kp_gk_rep_bits(const u32* pid, const u32* rep, u32 D, u32 m, u32* bits, u32 alloc) {   // bits: in/out
+    return guarded([&] {
+        need(alloc >= ((u64)m + 31) / 32, "bits holds a word per 32 phrases");
+        for (u32 k = 0; k < m; k++) need(pid[k] < D, "pid beyond rep");
+        Dev<u32> pi(pid, m), r(rep, D), b(bits, alloc);
+        gk::rep_bits(pi.p(), r.p(), m, b.p(), stream());
+        b.down(bits);
+    });
+}
+
+// ---- the context ------------------------------------------------------------------------------------------------------
+// gk::Ctx field for field, every table a host pointer with its length (tile0 and prof are the wrappers' own business; acgt,
+// acgt_lut and dense_ok come from gk::set_dense_codes as in guided.cpp, `no_dense` standing for the switch).  The phrase ends
+// come as bits (mask + rdir) or as a list (coff + brank), never both.  g_lcp: the values g_rmq is built over.
+struct KpCtx {
+    const KpText* T; u64 n; u32 w;
+    const u64* mask; u64 n_mask; const u32* rdir; u64 n_rdir; const u64* nxt; u64 n_nxt;
+    const u32* isa_p; u32 m; const u8* code; int bits, chars; u32 skip, pos_bits, rec_rank; u32 no_dense;
+    const u32* pid; const uint16_t* coff; u64 n_coff; const u32* brank; u64 n_brank;
+    const u32* g_k; const u64* g_ps; const u32* g_base; u32 g_n; const u32* g_isa; const u32* g_grp; const u32* g_lcp; u32 n_gisa;
+    u32 g_depth; const u32* g_bits; const u32* g_rank; const u32* repbits; u32 n_bitwords; u32 expand;
+};
+struct KpRunSlice { u32 sym, blo, bhi; const u64* lead; const u8* first; const u8* follow; u64 n_tiles; };
+
+struct DevCtx {
+    DevText t;
+    Dev<u64> mask, nxt, g_ps;
+    Dev<u32> rdir, isa_p, pid, brank, g_k, g_base, g_isa, g_grp, g_lcp, g_bits, g_rank, repbits;
+    Dev<uint16_t> coff;
+    Dev<u8> code;
+    DevBuf<u32> g_bmin;
+    gk::Ctx c;
+    std::vector<u64> cuts;                      // the phrase ends the tables spell, for the checks of indices that depend on a rank
+    u64 tiles;
+    explicit DevCtx(const KpCtx* k)
+        : t(k->T), mask(k->mask, k->mask ? k->n_mask : 0), nxt(k->nxt, k->n_nxt), g_ps(k->g_ps, k->g_n),
+          rdir(k->rdir, k->rdir ? k->n_rdir : 0), isa_p(k->isa_p, k->isa_p ? k->m : 0), pid(k->pid, k->pid ? k->m : 0),
+          brank(k->brank, k->brank ? k->n_brank : 0), g_k(k->g_k, k->g_n), g_base(k->g_base, k->g_n), g_isa(k->g_isa, k->n_gisa),
+          g_grp(k->g_grp, k->n_gisa), g_lcp(k->g_lcp, k->n_gisa), g_bits(k->g_bits, k->g_n ? k->n_bitwords : 0),
+          g_rank(k->g_rank, k->g_n ? k->n_bitwords : 0), repbits(k->repbits, k->repbits ? k->n_bitwords : 0),
+          coff(k->coff, k->coff ? k->n_coff : 0), code(k->code, 256) {
+        const u64 n = k->n, blocks = n / 4096 + 2;
+        need(n >= 1 && n == k->T->n && k->w >= 1 && k->w <= 32, "n = text length >= 1, 1 <= w <= 32");
+        need(k->bits >= 1 && k->chars >= 1 && k->bits * k->chars <= 63, "1 <= bits * chars <= 63");
+        need(k->code && k->code[0] == 0 && k->nxt, "a code table (code[0] = 0) and nxt");
+        need(k->pos_bits >= 1 && k->pos_bits <= 63 && (k->rec_rank || k->pos_bits == 40), "pos_bits 1 .. 63, 40 when the records carry lengths");
+        need((k->mask && k->rdir && !k->coff && !k->brank) || (!k->mask && !k->rdir && k->coff && k->brank), "the phrase ends as bits or as a list");
+        need(k->n_nxt >= blocks, "nxt holds n / 4096 + 2 entries");
+        for (u64 b = 0; b < k->n_nxt; b++) need(k->nxt[b] <= n + k->w - 1, "nxt at most n + w - 1");
+        if (k->mask) {
+            need(k->n_mask >= blocks * 64 && k->n_rdir >= blocks * 8, "mask holds n / 4096 + 2 blocks of 64 words, rdir a count per 8 words");
+            for (u64 wi = 0; wi < k->n_mask; wi++)
+                for (u64 x = k->mask[wi]; x; x &= x - 1) cuts.push_back(wi * 64 + (u64)__builtin_ctzll(x));
+        } else {
+            need(k->n_brank >= blocks + 2, "brank holds n / 4096 + 4 entries");
+            for (u64 b = 0; b + 1 < k->n_brank; b++) {
+                need(k->brank[b] <= k->brank[b + 1] && k->brank[b + 1] <= k->n_coff, "brank ascends within coff");
+                for (u32 e = k->brank[b]; e < k->brank[b + 1]; e++) {
+                    need(k->coff[e] < 4096 && (e == k->brank[b] || k->coff[e] > k->coff[e - 1]), "coff ascends inside a block, below 4096");
+                    cuts.push_back(b * 4096 + k->coff[e]);
+                }
+            }
+        }
+        need(cuts.empty() || cuts.back() < n, "phrase ends below n");
+        need(k->m >= cuts.size() + 1, "m counts a phrase per phrase end and the last");
+        need(k->isa_p || k->skip || k->expand, "isa_p unless the elements are phrases or representatives");
+        need(k->n_bitwords >= ((u64)k->m + 31) / 32 || !(k->repbits || k->g_n), "a bit per phrase in repbits / g_bits");
+        need(!k->g_n || (k->g_k && k->g_ps && k->g_base && k->g_isa && k->g_grp && k->g_lcp && k->g_bits && k->g_rank && k->n_gisa >= 1), "the giant tables");
+        tiles = std::max<u64>(1, (n + 4095) / 4096);
+        c.T = t.T; c.n = n; c.w = k->w; c.mask = k->mask ? mask.p() : nullptr; c.rdir = k->rdir ? rdir.p() : nullptr; c.nxt = nxt.p();
+        c.isa_p = k->isa_p ? isa_p.p() : nullptr; c.m = k->m; c.code = code.p(); c.bits = k->bits; c.chars = k->chars;
+        c.skip = k->skip; c.pos_bits = k->pos_bits; c.rec_rank = k->rec_rank;
+        gk::set_dense_codes(c, k->code, k->no_dense != 0);
+        c.pid = k->pid ? pid.p() : nullptr; c.coff = k->coff ? coff.p() : nullptr; c.brank = k->brank ? brank.p() : nullptr;
+        c.repbits = k->repbits ? repbits.p() : nullptr; c.expand = k->expand; c.g_depth = k->g_depth; c.g_n = k->g_n;
+        if (k->g_n) {
+            c.g_k = g_k.p(); c.g_ps = g_ps.p(); c.g_base = g_base.p(); c.g_isa = g_isa.p(); c.g_grp = g_grp.p();
+            c.g_bits = g_bits.p(); c.g_rank = g_rank.p();
+            u32 levels = 0;
+            c.g_rmq.sl = g_lcp.p(); c.g_rmq.m = k->n_gisa;
+            build_rmq(g_lcp.p(), k->n_gisa, g_bmin, c.g_rmq.nb, levels, stream());
+            c.g_rmq.bmin = g_bmin.get();
+        }
+    }
+    // |alpha| of an element as the kernels read it: from the record, or from the phrase ends
+    u64 len_of(const KpCtx* k, u64 rec) const {
+        const u64 q = rec & ((1ull << k->pos_bits) - 1);
+        const u64 len = rec >> 40;
+        if (!k->rec_rank && len != gk::LEN_SAT) return len;
+        const u64 x = q + k->skip + k->w - 2;
+        const auto it = std::lower_bound(cuts.begin(), cuts.end(), x);
+        return (x < c.n && it != cuts.end() ? *it : c.n + k->w - 1) + 2 - q;
+    }
+    // the giant tables as a whole: occurrence j is phrase g_k[j] (ascending, flagged in g_bits, counted by g_rank), begins at
+    // g_ps[j], and its whole phrase lies inside the dictionary from g_base[j] on -- then every entry a comparison asks for
+    // (an element of that phrase, a place before the end of its alpha) is inside g_isa; entries and groups inside the tables
+    void check_giant_tables(const KpCtx* k) const {
+        if (!k->g_n) return;
+        u32 seen = 0;
+        for (u32 ph = 0; ph < k->m; ph++) {
+            const u32 word = k->g_bits[ph >> 5];
+            if ((ph & 31) == 0) need(k->g_rank[ph >> 5] == seen, "g_rank counts the bits of g_bits");
+            if (!((word >> (ph & 31)) & 1u)) continue;
+            need(seen < k->g_n && k->g_k[seen] == ph, "g_k lists the phrases flagged in g_bits");
+            const u64 start = ph == 0 ? 0 : cuts[ph - 1] - k->w + 2, end = ph < cuts.size() ? cuts[ph] + 1 : c.n + k->w;
+            need(ph == 0 || cuts[ph - 1] + 2 >= k->w, "a phrase start inside V");
+            need(k->g_ps[seen] == start && (u64)k->g_base[seen] + (end - start + 1) <= k->n_gisa, "a giant occurrence begins at its phrase and lies inside the dictionary");
+            seen++;
+        }
+        need(seen == k->g_n, "g_n counts the flagged phrases");
+        for (u32 r = 0; r < k->n_gisa; r++) need(k->g_isa[r] < k->n_gisa, "g_isa inside the dictionary");
+    }
+    // elements whose alphas are compared character by character: every character of alpha inside V (forged lengths too), the
+    // shared prefix not longer than alpha, and giant tables that hold every entry a comparison may ask for
+    void check_compared(const KpCtx* k, const u64* pos, u32 count, u64 offset) const {
+        check_giant_tables(k);
+        check_elements(k, pos, count);
+        for (u32 e = 0; e < count; e++) {
+            const u64 q = pos[e] & ((1ull << k->pos_bits) - 1), len = len_of(k, pos[e]);
+            need(offset <= len && q + len <= c.n + 40, "alpha inside V, the shared prefix inside alpha");
+        }
+    }
+    // the rank of the parse suffix behind an element, as rec_rank_key reads it
+    u64 rank_key(const KpCtx* k, u64 rec) const {
+        if (k->rec_rank) return rec >> k->pos_bits;
+        const u32 ph = rank1((rec & ((1ull << k->pos_bits) - 1)) + k->skip + k->w - 2);
+        return ph + 1 < k->m ? k->isa_p[ph + 1] : 0;
+    }
+    u32 rank1(u64 x) const { return (u32)(std::lower_bound(cuts.begin(), cuts.end(), std::min(x, c.n)) - cuts.begin()); }
+    // every element of a list: a V index inside the text (1 .. n; a list of phrases may hold the first phrase, at 0)
+    void check_elements(const KpCtx* k, const u64* pos, u32 count) const {
+        for (u32 e = 0; e < count; e++) {
+            const u64 q = pos[e] & ((1ull << k->pos_bits) - 1);
+            need(q <= c.n && (q >= 1 || k->skip), "an element's V index is 1 .. n (0: the first phrase)");
+        }
+    }
+};
+struct DevRun {
+    Dev<u64> lead; Dev<u8> first, follow;
+    gk::RunSlice rs;
+    DevRun(const KpRunSlice* r, u64 tiles)
+        : lead(r ? r->lead : nullptr, r && r->sym ? r->n_tiles : 0), first(r ? r->first : nullptr, r && r->sym ? r->n_tiles : 0),
+          follow(r ? r->follow : nullptr, r && r->sym ? r->n_tiles : 0) {
+        if (!r || !r->sym) return;
+        need(r->lead && r->first && r->follow && r->n_tiles <= tiles + 1, "a run slice names its three tables, a tile behind the text's last at most");
+        need(r->blo <= r->bhi && r->bhi <= 2 * gk::RUN_BUCKETS_HALF, "buckets within 2 * RUN_BUCKETS_HALF");
+        rs.sym = r->sym; rs.blo = r->blo; rs.bhi = r->bhi; rs.lead = lead.p(); rs.first = first.p(); rs.follow = follow.p(); rs.n_tiles = r->n_tiles;
+    }
+};
+static void need_text_order(const KpCtx* k, int pc) {
+    need(!k->skip && pc >= 1 && pc <= k->chars && k->bits * pc <= 20, "text suffixes; 1 <= prefix_chars <= chars, bins of at most 20 bits");
+}
+
+// ---- text-order kernels -----------------------------------------------------------------------------------------------------
+// first, follow (alloc bytes), lead (alloc entries): in/out
+KP int kp_gk_tile_lead(const KpCtx* k, u8* first, uint16_t* lead, u8* follow, u32 alloc) {
+    return guarded([&] {
+        DevCtx d(k);
+        need(!k->skip && alloc >= d.tiles, "text suffixes; the tables hold a tile each");
+        Dev<u8> f(first, alloc), fo(follow, alloc);
+        Dev<uint16_t> l(lead, alloc);
+        gk::tile_lead(d.c, f.p(), l.p(), fo.p(), stream());
+        f.down(first); l.down(lead); fo.down(follow);
+    });
+}
+// hist (alloc entries): in/out, 4 * RUN_BUCKETS_HALF of them may be added to
+KP int kp_gk_run_hist(const KpCtx* k, int pc, u32 bin, const KpRunSlice* r, u64* hist, u32 alloc) {
+    return guarded([&] {
+        DevCtx d(k);
+        need_text_order(k, pc);
+        need(r && r->sym && alloc >= 4 * gk::RUN_BUCKETS_HALF, "a run slice; hist holds 4 * RUN_BUCKETS_HALF entries");
+        DevRun dr(r, d.tiles);
+        Dev<u64> h(hist, alloc);
+        gk::run_hist(d.c, pc, bin, dr.rs, h.p(), stream());
+        h.down(hist);
+    });
+}
+KP int kp_gk_bin_hist(const KpCtx* k, int pc, u64* hist, u32 alloc) {                         // hist: in/out (added to)
+    return guarded([&] {
+        DevCtx d(k);
+        need_text_order(k, pc);
+        need(pc <= 5 && alloc >= (1u << (k->bits * pc)), "at most five leading characters; hist holds a counter per bin");
+        Dev<u64> h(hist, alloc);
+        gk::bin_hist(d.c, pc, h.p(), stream());
+        h.down(hist);
+    });
+}
+KP int kp_gk_batch_count(const KpCtx* k, int pc, u32 bin_lo, u32 bin_hi, const KpRunSlice* r, u32* tile_count, u32 alloc) {
+    return guarded([&] {
+        DevCtx d(k);
+        need_text_order(k, pc);
+        need(alloc >= d.tiles, "tile_count holds a tile each");
+        DevRun dr(r, d.tiles);
+        Dev<u32> tc(tile_count, alloc);
+        gk::batch_count(d.c, pc, bin_lo, bin_hi, tc.p(), stream(), dr.rs);
+        tc.down(tile_count);
+    });
+}
+// tile_off: a tile each; keys, pos (alloc entries), next_count (count_alloc entries, or null): in/out.  A tile selects 4096
+// suffixes at the most: the lists must hold that many behind every tile's offset (what a tile does select is the kernel's answer).
+KP int kp_gk_batch_fill(const KpCtx* k, int pc, u32 bin_lo, u32 bin_hi, const u32* tile_off, u64* keys, u64* pos, u32 alloc, u32 next_lo,
+                        u32 next_hi, u32* next_count, u32 count_alloc, const KpRunSlice* r) {
+    return guarded([&] {
+        DevCtx d(k);
+        need_text_order(k, pc);
+        need(!next_count || count_alloc >= d.tiles, "next_count holds a tile each");
+        for (u64 t = 0; t < d.tiles; t++) need((u64)tile_off[t] + 4096 <= alloc, "tile_off + 4096 beyond the lists");
+        DevRun dr(r, d.tiles);
+        Dev<u32> to(tile_off, d.tiles), nc(next_count, next_count ? count_alloc : 0);
+        Dev<u64> dk(keys, alloc), dp(pos, alloc);
+        gk::batch_fill(d.c, pc, bin_lo, bin_hi, to.p(), dk.p(), dp.p(), next_lo, next_hi, next_count ? nc.p() : nullptr, stream(), dr.rs);
+        dk.down(keys); dp.down(pos); nc.down(next_count);
+    });
+}
+KP int kp_gk_stage_fill(const KpCtx* k, int pc, u32 bin_lo, u32 bin_hi, const u32* tile_off, u32* staged, u32 alloc, u32 next_lo, u32 next_hi,
+                        u32* next_count, u32 count_alloc) {
+    return guarded([&] {
+        DevCtx d(k);
+        need_text_order(k, pc);
+        need(!next_count || count_alloc >= d.tiles, "next_count holds a tile each");
+        for (u64 t = 0; t < d.tiles; t++) need((u64)tile_off[t] + 4096 <= alloc, "tile_off + 4096 beyond the lists");
+        Dev<u32> to(tile_off, d.tiles), nc(next_count, next_count ? count_alloc : 0), st(staged, alloc);
+        gk::stage_fill(d.c, pc, bin_lo, bin_hi, to.p(), st.p(), next_lo, next_hi, next_count ? nc.p() : nullptr, stream());
+        st.down(staged); nc.down(next_count);
+    });
+}
+// staged: n entries; tile_off: a tile each; blk_tile, block_off: a block of 4096 entries each (blk_tile one more);
+// keys, pos (alloc entries), next_count (count_alloc entries, or null): in/out
+KP int kp_gk_stage_take(const KpCtx* k, const u32* staged, u64 n, u32 b0, u32 b1, const u32* block_off, u64* keys, u64* pos, u32 alloc,
+                        u32 nb0, u32 nb1, u32* next_count, u32 count_alloc, const u32* tile_off, const u32* blk_tile) {
+    return guarded([&] {
+        DevCtx d(k);
+        need(!k->skip && n < (1ull << 32), "text suffixes; a list below 2^32 entries");
+        const u64 blocks = (n + 4095) / 4096;
+        need(!next_count || count_alloc >= blocks, "next_count holds a block each");
+        for (u64 b = 0; b < blocks; b++) need((u64)block_off[b] + 4096 <= alloc, "block_off + 4096 beyond the lists");
+        for (u64 b = 0; b <= blocks && n; b++) need(blk_tile[b] < d.tiles && (b == 0 || blk_tile[b] >= blk_tile[b - 1]), "blk_tile ascends below the number of tiles");
+        for (u64 t = 1; t < d.tiles; t++) need(tile_off[t] >= tile_off[t - 1], "tile_off ascends");
+        for (u64 i = 0; i < n; i++) {           // the text position an entry names: its tile is the last whose offset is at most i
+            const u64 t = (u64)(std::upper_bound(tile_off, tile_off + d.tiles, (u32)i) - tile_off);
+            need(t >= 1 && (t - 1) * 4096 + (staged[i] & 4095u) < k->n, "a staged entry beyond the text");
+            need(blk_tile[i >> 12] <= t - 1 && t - 1 <= blk_tile[(i >> 12) + 1], "blk_tile: a block's tiles lie between its entry and the next");
+        }
+        Dev<u32> st(staged, n), bo(block_off, blocks), nc(next_count, next_count ? count_alloc : 0), to(tile_off, d.tiles), bt(blk_tile, blocks + 1);
+        Dev<u64> dk(keys, alloc), dp(pos, alloc);
+        gk::stage_take(d.c, st.p(), n, b0, b1, bo.p(), dk.p(), dp.p(), nb0, nb1, next_count ? nc.p() : nullptr, to.p(), bt.p(), stream());
+        dk.down(keys); dp.down(pos); nc.down(next_count);
+    });
+}
+// pstart: n_phrases entries; keys, pos (alloc entries): in/out
+KP int kp_gk_phrase_items(const KpCtx* k, const void* pstart, int wide, u32 n_phrases, const u32* rep, u32 D, u64* keys, u64* pos, u32 alloc) {
+    return guarded([&] {
+        DevCtx d(k);
+        need(alloc >= D, "keys / pos hold D entries");
+        for (u32 i = 0; i < D; i++) need(rep[i] < n_phrases && pos_at(pstart, wide != 0, rep[i]) <= k->n, "rep beyond the phrases, or a phrase start beyond the text");
+        DevPos ps(pstart, n_phrases, wide != 0);
+        Dev<u32> r(rep, D);
+        Dev<u64> dk(keys, alloc), dp(pos, alloc);
+        gk::phrase_items(d.c, ps.p(), wide != 0, r.p(), D, dk.p(), dp.p(), stream());
+        dk.down(keys); dp.down(pos);
+    });
+}
+
+// ---- rounds and results that read the context ------------------------------------------------------------------------------
+// the entry of the giant dictionary an element at V index q would be given at `off`: the index must lie inside g_isa
+static void check_giant_entry(const DevCtx& d, const KpCtx* k, u64 rec, u64 off) {
+    if (!k->g_n) return;
+    const u64 q = rec & ((1ull << k->pos_bits) - 1);
+    if (off >= d.len_of(k, rec)) return;       // (only where alpha goes on at `off`: the kernels ask for no entry behind a spent alpha)
+    const u32 ph = d.rank1(q + k->skip + k->w - 2);
+    const u32 word = k->g_bits[ph >> 5];
+    if (!((word >> (ph & 31)) & 1u)) return;
+    const u32 lo = k->g_rank[ph >> 5] + (u32)__builtin_popcount(word & ((1u << (ph & 31)) - 1u));
+    need(lo < k->g_n && k->g_k[lo] == ph, "g_bits / g_rank / g_k name the same giant occurrences");
+    need(q + off >= k->g_ps[lo] && (u64)k->g_base[lo] + (q + off - k->g_ps[lo]) < k->n_gisa, "an element's giant entry beyond g_isa");
+}
+// keys (alloc entries), err (16 words): in/out; gr, pure, ghead: m entries each, or all null
+KP int kp_gk_round_keys(const KpCtx* k, const u64* pos, u32 m, u64 offset, u64* keys, u32 alloc, u32* err, const u32* gr, const u8* pure,
+                        const u32* ghead) {
+    return guarded([&] {
+        DevCtx d(k);
+        need(alloc >= m && ((gr && pure && ghead) || (!gr && !pure && !ghead)), "keys holds m entries; gr, pure and ghead together");
+        d.check_elements(k, pos, m);
+        for (u32 e = 0; e < m; e++) {
+            need(!ghead || ghead[e] < m, "ghead beyond the list");
+            check_giant_entry(d, k, pos[e], offset);
+        }
+        need(offset <= k->n + 64, "offset within the text");
+        Dev<u64> p(pos, m), dk(keys, alloc);
+        Dev<u32> e(err, 16), g(gr, gr ? m : 0), gh(ghead, ghead ? m : 0);
+        Dev<u8> pu(pure, pure ? m : 0);
+        gk::round_keys(d.c, p.p(), m, offset, dk.p(), e.p(), stream(), gr ? g.p() : nullptr, pure ? pu.p() : nullptr, ghead ? gh.p() : nullptr);
+        dk.down(keys); e.down(err);
+    });
+}
+// gr, pure (alloc entries): in/out
+KP int kp_gk_giant_probe(const KpCtx* k, const u64* pos, const u32* ghead, u32 m, u64 offset, u32* gr, u8* pure, u32 alloc) {
+    return guarded([&] {
+        DevCtx d(k);
+        need(alloc >= m, "gr / pure hold m entries");
+        d.check_elements(k, pos, m);
+        for (u32 e = 0; e < m; e++) { need(ghead[e] < m, "ghead beyond the list"); check_giant_entry(d, k, pos[e], offset); }
+        Dev<u64> p(pos, m);
+        Dev<u32> gh(ghead, m), g(gr, alloc);
+        Dev<u8> pu(pure, alloc);
+        gk::giant_probe(d.c, p.p(), gh.p(), m, offset, g.p(), pu.p(), stream());
+        g.down(gr); pu.down(pure);
+    });
+}
+// headval (alloc entries), err (16 words), lcp_out (lcp_alloc entries, or null; then slot is null too): in/out
+KP int kp_gk_round_heads(const KpCtx* k, const u64* keys, const u32* ghead, u32 m, u32* headval, u32 alloc, u32* err, u32* lcp_out,
+                         u32 lcp_alloc, const u32* slot, u64 offset, const u8* pure) {
+    return guarded([&] {
+        DevCtx d(k);
+        need(alloc >= m && (!lcp_out) == (!slot), "headval holds m entries; lcp_out and slot together");
+        check_gheads(ghead, m);
+        const bool giant_round = k->g_n != 0 && offset >= k->g_depth;
+        for (u32 c = 0; c < m; c++) {
+            need(!slot || slot[c] < lcp_alloc, "slot beyond lcp_out");
+            const bool as_giant = (giant_round || (pure && pure[ghead[c]])) && (keys[c] >> 32) == (gk::GIANT_KEY >> 32);
+            need(!as_giant || (k->g_n && (u32)keys[c] < k->n_gisa), "a giant key beyond the giant dictionary");
+            // two entries of different groups inside one old group: ascending, as the round's sort leaves them (the range minimum
+            // between them is asked for)
+            if (as_giant && c > 0 && ghead[c] != c && (keys[c - 1] >> 32) == (gk::GIANT_KEY >> 32) && (u32)keys[c - 1] < k->n_gisa &&
+                k->g_grp[(u32)keys[c]] != k->g_grp[(u32)keys[c - 1]])
+                need((u32)keys[c - 1] < (u32)keys[c], "giant entries of one group ascend");
+        }
+        Dev<u64> dk(keys, m);
+        Dev<u32> gh(ghead, m), hv(headval, alloc), e(err, 16), l(lcp_out, lcp_out ? lcp_alloc : 0), sl(slot, slot ? m : 0);
+        Dev<u8> pu(pure, pure ? m : 0);
+        gk::round_heads(d.c, dk.p(), gh.p(), m, hv.p(), e.p(), stream(), lcp_out ? l.p() : nullptr, slot ? sl.p() : nullptr, offset,
+                        pure ? pu.p() : nullptr);
+        hv.down(headval); e.down(err); l.down(lcp_out);
+    });
+}
+// sa_lo (alloc entries), sa_hi (alloc bytes, or null: a 32-bit column), bwt (alloc bytes): in/out
+KP int kp_gk_write_columns(const KpCtx* k, const u64* pos, u32 B, u64 base, u32* sa_lo, u8* sa_hi, u8* bwt, u32 alloc) {
+    return guarded([&] {
+        DevCtx d(k);
+        need(base + B <= alloc && !k->skip, "the columns hold base + B entries; text suffixes");
+        d.check_elements(k, pos, B);
+        Dev<u64> p(pos, B);
+        Dev<u32> lo(sa_lo, alloc);
+        Dev<u8> hi(sa_hi, sa_hi ? alloc : 0), bw(bwt, alloc);
+        SaCol col; col.lo = lo.p(); col.hi = sa_hi ? hi.p() : nullptr;
+        gk::write_columns(d.c, p.p(), B, base, col, bw.p(), stream());
+        lo.down(sa_lo); hi.down(sa_hi); bw.down(bwt);
+    });
+}
+// pid: the context's (m entries); prank (alloc entries): in/out
+KP int kp_gk_phrase_ranks(const KpCtx* k, const u64* pos, u32 D, const u32* pid, u32* prank, u32 alloc) {
+    return guarded([&] {
+        DevCtx d(k);
+        d.check_elements(k, pos, D);
+        for (u32 j = 0; j < D; j++) need(pid[d.rank1((pos[j] & ((1ull << k->pos_bits) - 1)) + k->skip + k->w - 2)] < alloc, "pid beyond prank");
+        Dev<u64> p(pos, D);
+        Dev<u32> pi(pid, k->m), pr(prank, alloc);
+        gk::phrase_ranks(d.c, p.p(), D, pi.p(), pr.p(), stream());
+        pr.down(prank);
+    });
+}
+// tab: n_tab records of four words; the seven columns (alloc entries), err (16 words): in/out
+KP int kp_gk_expand_entries(const KpCtx* k, const u64* pos, const u32* lcp, u32 B, const u32* tab, u32 n_tab, u32* ce_cnt, u32* ce_first,
+                            u32* ce_offm1, u8* ce_bwt, u32* ce_gs, u32* ce_hl, u32* ce_slen, u32 alloc, u32* err) {
+    return guarded([&] {
+        DevCtx d(k);
+        need(alloc >= B && k->pid && !k->skip, "the columns hold B entries; the context names pid; text suffixes");
+        d.check_elements(k, pos, B);
+        for (u32 e = 0; e < B; e++) need(k->pid[d.rank1((pos[e] & ((1ull << k->pos_bits) - 1)) + k->skip + k->w - 2)] < n_tab, "pid beyond tab");
+        Dev<u64> p(pos, B);
+        Dev<u32> l(lcp, B), tb(tab, 4 * (size_t)n_tab), c0(ce_cnt, alloc), c1(ce_first, alloc), c2(ce_offm1, alloc), c4(ce_gs, alloc),
+            c5(ce_hl, alloc), c6(ce_slen, alloc), e(err, 16);
+        Dev<u8> c3(ce_bwt, alloc);
+        gk::expand_entries(d.c, p.p(), l.p(), B, tb.p(), c0.p(), c1.p(), c2.p(), c3.p(), c4.p(), c5.p(), c6.p(), e.p(), stream());
+        c0.down(ce_cnt); c1.down(ce_first); c2.down(ce_offm1); c3.down(ce_bwt); c4.down(ce_gs); c5.down(ce_hl); c6.down(ce_slen); e.down(err);
+    });
+}
+
+// out (out_alloc entries), flags (alloc entries), err (16 words), lcp_out (out_alloc entries, or null): in/out
+KP int kp_gk_resolve_small(const KpCtx* k, const u64* pos, const u32* ghead, const u32* slot, u32 m, u64 offset, u64* out, u32 out_alloc,
+                           u8* flags, u32 alloc, u32* err, u32* lcp_out, u32 limit) {
+    return guarded([&] {
+        DevCtx d(k);
+        need(alloc >= m, "flags holds m entries");
+        check_gheads(ghead, m);
+        d.check_compared(k, pos, m, offset);
+        for (u32 e = 0; e < m; e++)                          // a group's slots are consecutive from its first member's
+            need((u64)slot[ghead[e]] + (e - ghead[e]) < out_alloc, "a group's slots beyond out");
+        Dev<u64> p(pos, m), o(out, out_alloc);
+        Dev<u32> gh(ghead, m), sl(slot, m), e(err, 16), l(lcp_out, lcp_out ? out_alloc : 0);
+        Dev<u8> f(flags, alloc);
+        gk::resolve_small(d.c, p.p(), gh.p(), sl.p(), m, offset, o.p(), f.p(), e.p(), stream(), lcp_out ? l.p() : nullptr, limit);
+        o.down(out); f.down(flags); e.down(err); l.down(lcp_out);
+    });
+}
+// sl: the parse's LCP values (n_sl entries: the range-minimum view is built over them); carry: one record, or null;
+// lcp (alloc entries), err (16 words): in/out
+KP int kp_gk_batch_lcp(const KpCtx* k, const u32* sl, u32 n_sl, const u64* pos, u32 B, const u64* carry, u32* lcp, u32 alloc, u32* err) {
+    return guarded([&] {
+        DevCtx d(k);
+        need(alloc >= B && n_sl >= 1, "lcp holds B entries; sl at least one");
+        d.check_compared(k, pos, B, 0);
+        if (carry) d.check_compared(k, carry, 1, 0);
+        for (u32 j = 0; j < B && !k->expand; j++) need(d.rank_key(k, pos[j]) < n_sl, "a parse rank beyond sl");
+        need(!carry || k->expand || d.rank_key(k, carry[0]) < n_sl, "a parse rank beyond sl");
+        Dev<u64> p(pos, B), cy(carry, carry ? 1 : 0);
+        Dev<u32> v(sl, n_sl), l(lcp, alloc), e(err, 16);
+        DevBuf<u32> bmin;
+        RmqView R;
+        R.sl = v.p(); R.m = n_sl;
+        u32 levels = 0;
+        build_rmq(v.p(), n_sl, bmin, R.nb, levels, stream());
+        R.bmin = bmin.get();
+        gk::batch_lcp(d.c, R, p.p(), B, carry ? cy.p() : nullptr, carry != nullptr, l.p(), e.p(), stream());
+        l.down(lcp); e.down(err);
+    });
+}
+
+// list: 4 regions of cap (first, size) pairs, n_groups[cl] of them used; sl: the parse's LCP values (n_sl entries);
+// out (out_alloc entries), flags (alloc entries), lcp_out (out_alloc entries, or null), err (16 words): in/out
+KP int kp_gk_resolve_medium(const KpCtx* k, const u32* sl, u32 n_sl, const u64* pos, u32 m, const u32* slot, const u32* list, u32 cap,
+                            const u32* n_groups, u64 offset, u64* out, u32 out_alloc, u8* flags, u32 alloc, u32* lcp_out, u32* err) {
+    return guarded([&] {
+        DevCtx d(k);
+        need(alloc >= m && n_sl >= 1, "flags holds m entries; sl at least one");
+        d.check_compared(k, pos, m, offset);
+        for (u32 e = 0; e < m && !k->expand && !k->skip; e++) need(d.rank_key(k, pos[e]) < n_sl, "a parse rank beyond sl");
+        static const u32 seg[4] = {16, 32, 64, 128};
+        for (u32 cl = 0; cl < 4; cl++) {
+            need(n_groups[cl] <= cap, "a class has more groups than a region holds");
+            for (u32 g = 0; g < n_groups[cl]; g++) {
+                const u32 first = list[2 * ((size_t)cl * cap + g)], size = list[2 * ((size_t)cl * cap + g) + 1];
+                need(size >= 1 && size <= seg[cl] && (u64)first + size <= m, "a listed group inside the list, not larger than its class");
+                need((u64)slot[first] + size <= out_alloc, "a group's slots beyond out");
+            }
+        }
+        Dev<u64> p(pos, m), o(out, out_alloc);
+        Dev<u32> v(sl, n_sl), s2(slot, m), li(list, 8 * (size_t)cap), e(err, 16), l(lcp_out, lcp_out ? out_alloc : 0);
+        Dev<u8> f(flags, alloc);
+        DevBuf<u32> bmin;
+        RmqView R;
+        R.sl = v.p(); R.m = n_sl;
+        u32 levels = 0;
+        build_rmq(v.p(), n_sl, bmin, R.nb, levels, stream());
+        R.bmin = bmin.get();
+        gk::resolve_medium(d.c, R, p.p(), s2.p(), li.p(), cap, n_groups, offset, o.p(), f.p(), lcp_out ? l.p() : nullptr, e.p(), stream());
+        o.down(out); f.down(flags); l.down(lcp_out); e.down(err);
     });
 }
