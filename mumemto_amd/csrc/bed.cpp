@@ -10,25 +10,18 @@
 #include <vector>
 
 #include "bed_kernels.hpp"
+#include "contig_table.hpp"
 #include "laps.hpp"
-#include "piece_writer.hpp"
-#include "pool.hpp"
+#include "merged_tools.hpp"
 #include "prims.hpp"
-#include "switches.hpp"
+#include "text_pieces.hpp"
 
 namespace mmt {
 namespace {
 
-constexpr size_t REC_BYTES = bk::RECORD_FIELDS * 8;
-
 // room for `want` records in m.d_bed_records; the first `have` records stay
 void reserve_records(MergedRows& m, size_t have, size_t want, hipStream_t st) {
-    if (want * bk::RECORD_FIELDS <= m.d_bed_records.size()) return;
-    DevBuf<int64_t> bigger;
-    bigger.ensure(std::max(want * bk::RECORD_FIELDS, 2 * m.d_bed_records.size()));
-    if (have) MMT_HIP(hipMemcpyAsync(bigger.get(), m.d_bed_records.get(), have * REC_BYTES, hipMemcpyDeviceToDevice, st));
-    MMT_HIP(hipStreamSynchronize(st));
-    m.d_bed_records.swap(bigger);
+    grow_keep(m.d_bed_records, have * bk::RECORD_FIELDS, want * bk::RECORD_FIELDS, st);
 }
 
 // the number of set flags: the last flag and its number
@@ -56,12 +49,7 @@ uint64_t measure_column(Engine& e, const MergedRows& m, int64_t col, DevBuf<uint
     bytes.ensure(n_rec + 1); offset.ensure(n_rec + 1);
     bk::measure(m.d_bed_records.get() + r0 * bk::RECORD_FIELDS, (uint32_t)n_rec, m.d_bed_name_begin.get(), m.bed_contig_begin[col],
                 bytes.get(), st);
-    MMT_HIP(hipMemsetAsync(bytes.get() + n_rec, 0, 4, st));
-    prims::exclusive_sum_u32_to_u64(e.scratch(), bytes.get(), offset.get(), n_rec + 1, st);
-    uint64_t total = 0;
-    MMT_HIP(hipMemcpyAsync(&total, offset.get() + n_rec, 8, hipMemcpyDeviceToHost, st));
-    MMT_HIP(hipStreamSynchronize(st));
-    return total;
+    return line_offsets(e.scratch(), bytes.get(), offset.get(), n_rec, st);
 }
 
 // the lines of records [k0, k1) of column col at text[0 ..)
@@ -81,41 +69,12 @@ void bed(Engine& e, MergedRows& m, const uint64_t* contig_begin, const int64_t* 
     if (seq_idx < -1 || seq_idx >= (int64_t)m.n_docs)
         throw std::invalid_argument("bed: sequence index " + std::to_string(seq_idx) + " is out of range (-1 = all, 0-" +
                                     std::to_string((int64_t)m.n_docs - 1) + ")");
-    if (!contig_begin) throw std::invalid_argument("bed: contig_begin must hold n_docs + 1 entries");
     const uint32_t nd = (uint32_t)m.n_docs, n = (uint32_t)m.n_rows;
-    for (uint32_t c = 0; c < nd; c++)
-        if (contig_begin[c] > contig_begin[c + 1]) throw std::invalid_argument("bed: contig_begin does not ascend");
-    const uint64_t n_contigs = contig_begin[nd];
-    if (n_contigs && (!contig_len || !name_begin))
-        throw std::invalid_argument("bed: contig_len and name_begin must hold an entry per contig (name_begin one more)");
-    for (uint64_t g = 0; g < n_contigs; g++)
-        if (name_begin[g] > name_begin[g + 1]) throw std::invalid_argument("bed: name_begin does not ascend");
-    const uint64_t name_bytes = n_contigs ? name_begin[n_contigs] : 0;
-    if (name_bytes && !names) throw std::invalid_argument("bed: names must hold the bytes name_begin refers to");
     const uint32_t first = seq_idx < 0 ? 0 : (uint32_t)seq_idx, last = seq_idx < 0 ? nd : (uint32_t)seq_idx + 1;
-    // cumulative lengths per column; the columns asked for are checked
-    std::vector<int64_t> ends((size_t)n_contigs + 1, 0);
-    for (uint32_t c = 0; c < nd; c++) {
-        const bool needed = c >= first && c < last;
-        if (needed && contig_begin[c] == contig_begin[c + 1])
-            throw std::invalid_argument("bed: sequence " + std::to_string(c) + " has no contigs");
-        uint64_t run = 0;
-        for (uint64_t g = contig_begin[c]; g < contig_begin[c + 1]; g++) {
-            if (needed && contig_len[g] < 0)
-                throw std::invalid_argument("bed: contig " + std::to_string(g - contig_begin[c]) + " of sequence " + std::to_string(c) +
-                                            " has the negative length " + std::to_string(contig_len[g]));
-            run += (uint64_t)contig_len[g];
-            if (needed && run >> 62) throw std::invalid_argument("bed: sequence " + std::to_string(c) + " is 2^62 bases or longer");
-            ends[g] = (int64_t)run;
-            if (!needed) continue;
-            for (uint64_t i = name_begin[g]; i < name_begin[g + 1]; i++)
-                if (names[i] == '\t' || names[i] == '\n')
-                    throw std::invalid_argument("bed: the name of contig " + std::to_string(g - contig_begin[c]) + " of sequence " +
-                                                std::to_string(c) + " contains a tab or a newline");
-        }
-        if (needed && run == 0)
-            throw std::invalid_argument("bed: sequence " + std::to_string(c) + " has total length 0: no contig can hold an interval");
-    }
+    // the columns asked for are checked
+    const ContigTable table = check_contig_table({"bed", first, last, false, true, "\t\n", "an interval"}, nd, contig_begin, contig_len,
+                                                 name_begin, names);
+    const uint64_t n_contigs = table.n_contigs, name_bytes = table.name_bytes;
     hipStream_t st = e.stream();
     MMT_HIP(hipSetDevice(e.device()));
     DevBuf<uint8_t>& temp = e.scratch();
@@ -133,7 +92,7 @@ void bed(Engine& e, MergedRows& m, const uint64_t* contig_begin, const int64_t* 
     DevBuf<uint64_t> d_contig_begin, d_clamped;
     d_ends.ensure((size_t)n_contigs + 1); d_contig_begin.ensure((size_t)nd + 1); d_clamped.ensure(1);
     m.d_bed_name_begin.ensure((size_t)n_contigs + 1); m.d_bed_names.ensure((size_t)name_bytes + 1);
-    MMT_HIP(hipMemcpyAsync(d_ends.get(), ends.data(), ((size_t)n_contigs + 1) * 8, hipMemcpyHostToDevice, st));
+    MMT_HIP(hipMemcpyAsync(d_ends.get(), table.ends.data(), ((size_t)n_contigs + 1) * 8, hipMemcpyHostToDevice, st));
     MMT_HIP(hipMemcpyAsync(d_contig_begin.get(), contig_begin, ((size_t)nd + 1) * 8, hipMemcpyHostToDevice, st));
     const uint64_t zero = 0;
     MMT_HIP(hipMemcpyAsync(m.d_bed_name_begin.get(), n_contigs ? name_begin : &zero, ((size_t)n_contigs + 1) * 8,
@@ -164,12 +123,7 @@ void bed(Engine& e, MergedRows& m, const uint64_t* contig_begin, const int64_t* 
                 laps.end();
                 flag.release(); number.release();
                 reserve_records(m, 0, (size_t)n_cols * n_rec, st);
-                // the batch: as many columns of (begin, end, strand) as half of what the heap has free holds
-                size_t batch = n_cols;
-                const size_t avail = pool::available(e.device()) / 2, one_col = (size_t)n_rec * 17;
-                if (batch * one_col > avail) batch = avail / one_col;
-                batch = (size_t)sw::num(sw::MMT_COLLINEAR_BATCH, batch);
-                batch = std::min<size_t>(std::max<size_t>(batch, 1), n_cols);
+                const size_t batch = columns_per_batch(e.device(), n_cols, (size_t)n_rec * 17, 0);      // columns of (begin, end, strand)
                 begins.ensure(batch * n_rec); ends_of.ensure(batch * n_rec); strands.ensure(batch * n_rec);
                 for (uint32_t c0 = first; c0 < last; c0 += (uint32_t)batch) {
                     const uint32_t cols = std::min<uint32_t>((uint32_t)batch, last - c0);
@@ -256,7 +210,7 @@ std::string bed_text(Engine& e, const MergedRows& m, int64_t col, BedStats* stat
     return out;
 }
 
-// pieces of whole lines, each at most this many bytes (a single longer line is a piece of its own)
+// pieces of whole lines, each at most this many bytes (a single longer line is a piece of its own); MMT_MERGED_TEXT_PIECE sets it
 static constexpr size_t BED_TEXT_PIECE = (size_t)256 << 20;
 
 void bed_write_text(Engine& e, const MergedRows& m, int64_t col, const std::string& path, BedStats* stats) {
@@ -269,46 +223,9 @@ void bed_write_text(Engine& e, const MergedRows& m, int64_t col, const std::stri
     laps.begin(3);
     const uint64_t bytes = measure_column(e, m, col, offset);
     laps.end();
-    std::vector<size_t> cut(1, 0);
-    std::vector<uint64_t> h_off;
-    uint64_t longest = 0;
-    if (bytes <= BED_TEXT_PIECE) {
-        if (bytes) cut.push_back(n_rec);
-        h_off = {0, bytes};
-        longest = bytes;
-    } else {
-        h_off.resize(n_rec + 1);
-        MMT_HIP(hipMemcpyAsync(h_off.data(), offset.get(), (n_rec + 1) * 8, hipMemcpyDeviceToHost, st));
-        MMT_HIP(hipStreamSynchronize(st));
-        for (size_t r = 0; r < n_rec;) {
-            const uint64_t lim = h_off[r] + BED_TEXT_PIECE;
-            size_t q = (size_t)(std::upper_bound(h_off.begin() + r + 1, h_off.end(), lim) - h_off.begin()) - 1;
-            if (q <= r) q = r + 1;
-            longest = std::max<uint64_t>(longest, h_off[q] - h_off[r]);
-            cut.push_back(q);
-            r = q;
-        }
-    }
-    const bool one = bytes <= BED_TEXT_PIECE;
-    DevBuf<char> d_piece[2];
-    for (auto& d : d_piece) d.ensure((size_t)longest + 1);
-    PieceWriter writer((size_t)longest + 1, 2);
-    writer.open(path, e.device(), false);        // (left open by an exception: its destructor removes PATH.tmp)
-    for (size_t i = 0; i + 1 < cut.size(); i++) {
-        DevBuf<char>& d = d_piece[i & 1];
-        const size_t k0 = cut[i], k1 = cut[i + 1];
-        const uint64_t from = one ? 0 : h_off[k0], to = one ? bytes : h_off[k1];
-        PieceWriter::Piece pc = writer.room((size_t)(to - from));
-        laps.begin(3);
-        write_column(e, m, col, offset, k0, k1, from, d.get());
-        laps.end();
-        MMT_HIP(hipMemcpyAsync(pc.p, d.get(), pc.n, hipMemcpyDeviceToHost, st));
-        MMT_HIP(hipStreamSynchronize(st));
-        writer.push(pc);
-    }
-    MMT_HIP(hipStreamSynchronize(st));
-    laps.collect();
-    writer.close();
+    write_text_pieces(st, e.device(), offset.get(), n_rec, bytes, text_piece_bytes(BED_TEXT_PIECE), path,
+                      [&](size_t k0, size_t k1, uint64_t base, char* dst) { write_column(e, m, col, offset, k0, k1, base, dst); },
+                      {&laps, 3, -1});
     if (stats) stats->text_bytes += bytes;
 }
 

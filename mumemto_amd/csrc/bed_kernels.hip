@@ -5,14 +5,12 @@
 
 #include "bed_kernels.hpp"
 #include "device_utils.hpp"
+#include "launch_grid.hpp"
+#include "table_text.hpp"
 
 namespace mmt { namespace bk {
 
-// grid-stride kernels throughout: a launch stays far below 2^32 work-items for any count below 2^32
-static inline unsigned grid_capped(uint64_t items, unsigned per_block, uint64_t cap = 1ull << 20) {
-    const uint64_t g = (items + per_block - 1) / per_block;
-    return (unsigned)(g ? (g < cap ? g : cap) : 1);
-}
+using namespace tt;      // the decimals and the contig search
 
 // ---- select ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(SELECT_BLOCK) void k_select_flags(const int64_t* __restrict__ off, const uint32_t* __restrict__ length,
@@ -127,16 +125,6 @@ void gather(const int64_t* off, const uint8_t* st, const uint32_t* length, const
 }
 
 // ---- contig lookup --------------------------------------------------------------------------------------------------------
-// the first i in [0, cnt) with ends[i] > v, cnt when there is none
-__device__ __forceinline__ uint32_t upper_bound(const int64_t* ends, uint32_t cnt, int64_t v) {
-    uint32_t lo = 0, hi = cnt;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (ends[mid] > v) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(256) void k_lookup(const int64_t* __restrict__ begin, const int64_t* __restrict__ end,
                                                 const uint8_t* __restrict__ strand, const int64_t* __restrict__ name,
                                                 uint32_t n_rec, uint32_t c0, uint32_t n_cols,
@@ -183,20 +171,6 @@ void lookup(const int64_t* begin, const int64_t* end, const uint8_t* strand, con
 }
 
 // ---- text -----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t ndigits(uint64_t v) {
-    uint32_t d = 1;
-    while (v >= 10) { v /= 10; d++; }
-    return d;
-}
-__device__ __forceinline__ uint32_t width_of(int64_t v) { return v < 0 ? 1 + ndigits(0ull - (uint64_t)v) : ndigits((uint64_t)v); }
-__device__ __forceinline__ char* put_uint(char* dst, uint64_t v, uint32_t nd) {
-    for (uint32_t i = nd; i-- > 0;) { dst[i] = (char)('0' + v % 10); v /= 10; }
-    return dst + nd;
-}
-__device__ __forceinline__ char* put_int(char* dst, int64_t v) {
-    if (v < 0) { *dst++ = '-'; const uint64_t a = 0ull - (uint64_t)v; return put_uint(dst, a, ndigits(a)); }
-    return put_uint(dst, (uint64_t)v, ndigits((uint64_t)v));
-}
 // block_<b> for name >= 0, mum_<i> for name = -1 - i
 __device__ __forceinline__ uint32_t label_width(int64_t name) {
     return name >= 0 ? 6 + ndigits((uint64_t)name) : 4 + ndigits((uint64_t)(-1 - name));
@@ -208,7 +182,7 @@ __global__ void k_measure(const int64_t* __restrict__ records, uint32_t n_rec, c
     for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n_rec; k += stride) {
         const int64_t* rec = records + k * RECORD_FIELDS;
         const uint64_t g = first_contig + (uint64_t)rec[0];
-        bytes[k] = (uint32_t)(name_begin[g + 1] - name_begin[g]) + width_of(rec[1]) + width_of(rec[2]) + label_width(rec[3]) + 6;
+        bytes[k] = (uint32_t)(name_begin[g + 1] - name_begin[g]) + int_width(rec[1]) + int_width(rec[2]) + label_width(rec[3]) + 6;
     }
 }
 void measure(const int64_t* records, uint32_t n_rec, const uint64_t* name_begin, uint64_t first_contig, uint32_t* bytes,

@@ -12,16 +12,10 @@
 #include "collinear_kernels.hpp"
 #include "laps.hpp"
 #include "merge_kernels.hpp"
-#include "pool.hpp"
+#include "merged_tools.hpp"
 #include "prims.hpp"
 
 namespace mmt {
-namespace {
-
-int bit_width_u64(uint64_t v) { int b = 0; while (v) { b++; v >>= 1; } return b ? b : 1; }
-
-}  // namespace
-
 void collinear_blocks(Engine& e, MergedRows& m, uint32_t max_break, int64_t min_single, CollinearStats* stats) {
     if (m.n_rows > 0xffffffffull)
         throw std::runtime_error("collinear blocks: a table of 2^32 rows or more (" + std::to_string(m.n_rows) +
@@ -35,11 +29,7 @@ void collinear_blocks(Engine& e, MergedRows& m, uint32_t max_break, int64_t min_
     CollinearStats& S = stats ? *stats : local;
     S = CollinearStats();
     Laps laps(st, stats ? S.ms : nullptr);
-    m.has_blocks = false; m.n_blocks = 0;
-    m.has_calls = false; m.n_calls = 0;
-    m.has_coverage = false;                      // (a reading of the table this call replaces)
-    m.has_bed = false;
-    m.has_label = false;
+    m.table_replaced();                          // (this call filters and sorts the table)
     S.rows_in = m.n_rows;
 
     // ---- (1) MUMdata.filter_pmums + MUMdata.sort (utils.py:486-495, :323-361) -------------------------------------------
@@ -93,35 +83,27 @@ void collinear_blocks(Engine& e, MergedRows& m, uint32_t max_break, int64_t min_
     ck::pair_init(pair_cols.get(), pair_gap.get(), n, st);
     if (n >= 2) {
         DevBuf<uint64_t> keys, sorted_keys;
-        DevBuf<uint32_t> rows_in, rows_out, col_state;
+        DevBuf<uint32_t> rows_in, rows_out;
+        ColumnFlags flags;
         sorted_keys.ensure(n); rows_in.ensure(n); rows_out.ensure(n);
-        // the batch: as many columns of keys as half of what the heap has free holds, beside the buffers of one sort
-        size_t batch = nd;
-        const size_t avail = pool::available(e.device()) / 2, one_sort = (size_t)n * 24;
-        if ((size_t)nd * n * 8 + one_sort > avail) batch = avail > one_sort ? (avail - one_sort) / ((size_t)n * 8) : 1;
-        batch = (size_t)sw::num(sw::MMT_COLLINEAR_BATCH, batch);
-        batch = std::min<size_t>(std::max<size_t>(batch, 1), nd);
+        // columns of keys, beside the buffers of one sort
+        const size_t batch = columns_per_batch(e.device(), nd, (size_t)n * 8, (size_t)n * 24);
         keys.ensure(batch * n);
-        // per column: 1 = not ascending; behind them, 8-byte aligned, the 64-bit OR of the starts
-        const size_t or_at = (batch + 1) & ~(size_t)1;
-        col_state.ensure(or_at + 2);
+        flags.ensure(batch);
         ck::iota(rows_in.get(), n, st);
-        std::vector<uint32_t> h_state(or_at + 2);
         for (uint32_t c0 = 0; c0 < nd; c0 += (uint32_t)batch) {
             const uint32_t cols = std::min<uint32_t>((uint32_t)batch, nd - c0);
             laps.begin(1);
-            MMT_HIP(hipMemsetAsync(col_state.get(), 0, (or_at + 2) * 4, st));
-            ck::extract_columns(m.d_offsets.get(), m.d_strands.get(), n, nd, c0, cols, keys.get(), col_state.get(),
-                                reinterpret_cast<uint64_t*>(col_state.get() + or_at), st);
+            flags.clear(st);
+            ck::extract_columns(m.d_offsets.get(), m.d_strands.get(), n, nd, c0, cols, keys.get(), flags.state(),
+                                flags.key_or_device(), st);
             laps.end();
-            MMT_HIP(hipMemcpyAsync(h_state.data(), col_state.get(), (or_at + 2) * 4, hipMemcpyDeviceToHost, st));
-            MMT_HIP(hipStreamSynchronize(st));
-            const uint64_t key_or = (uint64_t)h_state[or_at] | ((uint64_t)h_state[or_at + 1] << 32);
-            if (key_or >> 63) throw std::runtime_error("collinear blocks: a negative start other than -1 in the table");
-            const int bits = bit_width_u64(key_or);
+            flags.read(st);
+            if (flags.key_or() >> 63) throw std::runtime_error("collinear blocks: a negative start other than -1 in the table");
+            const int bits = bit_width_u64(flags.key_or());
             for (uint32_t c = 0; c < cols; c++) {
                 const uint64_t* col = keys.get() + (size_t)c * n;
-                if (h_state[c] & 1u) {
+                if (flags.descends(c)) {
                     laps.begin(2);
                     prims::sort_pairs_u64_u32(temp, col, sorted_keys.get(), rows_in.get(), rows_out.get(), n, 0, bits, st);
                     laps.end();

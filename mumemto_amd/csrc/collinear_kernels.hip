@@ -5,14 +5,9 @@
 
 #include "collinear_kernels.hpp"
 #include "device_utils.hpp"
+#include "launch_grid.hpp"
 
 namespace mmt { namespace ck {
-
-// grid-stride kernels throughout: a launch stays far below 2^32 work-items for any row count below 2^32
-static inline unsigned grid_capped(uint64_t items, unsigned per_block) {
-    const uint64_t g = (items + per_block - 1) / per_block;
-    return (unsigned)(g ? (g < (1ull << 20) ? g : (1ull << 20)) : 1);
-}
 
 __global__ void k_full_row_flags(const int64_t* __restrict__ off, uint32_t n, uint32_t n_docs, uint8_t* __restrict__ flags) {
     const uint32_t lane = threadIdx.x & 63;
@@ -48,16 +43,23 @@ void anchor_keys(const int64_t* off, const uint32_t* rows, uint32_t m, uint32_t 
     MMT_HIP(hipGetLastError());
 }
 
-// A tile is TR rows x TC columns.  Read: the 32 lanes of a half-wave take 32 consecutive cells of one row (256 contiguous
-// bytes), 8 rows per step.  Write: a wave takes 64 consecutive rows of one column (512 contiguous bytes).  The LDS tile is
-// [column][row] with one key of padding per column: the read phase writes with a stride of 65 keys = 130 dwords across
-// lanes (distinct even banks over a half-wave), the write phase reads consecutive keys.
+// A tile is TR items x TC columns; item i is row i of the table, or with BLOCK_HEADS the first row lr[2 i] of block i.  Read:
+// the 32 lanes of a half-wave take 32 consecutive cells of one row (256 contiguous bytes), 8 rows per step.  Write: a wave
+// takes 64 consecutive items of one column (512 contiguous bytes).  The LDS tile is [column][item] with one key of padding
+// per column: the read phase writes with a stride of 65 keys = 130 dwords across lanes (distinct even banks over a
+// half-wave), the write phase reads consecutive keys.
 constexpr uint32_t TR = 64, TC = 32;
 
-__global__ __launch_bounds__(256) void k_extract_columns(const int64_t* __restrict__ off, const uint8_t* __restrict__ st, uint32_t n,
-                                                         uint32_t n_docs, uint32_t c0, uint32_t n_cols,
-                                                         uint64_t* __restrict__ keys, uint32_t* __restrict__ col_state,
-                                                         unsigned long long* __restrict__ key_or) {
+template <bool BLOCK_HEADS>
+__device__ __forceinline__ uint64_t row_of(const uint32_t* __restrict__ lr, uint64_t i) {
+    return BLOCK_HEADS ? (uint64_t)lr[2 * i] : i;
+}
+
+template <bool BLOCK_HEADS>
+__global__ __launch_bounds__(256) void k_extract(const int64_t* __restrict__ off, const uint8_t* __restrict__ st,
+                                                 const uint32_t* __restrict__ lr, uint32_t n, uint32_t n_docs, uint32_t c0,
+                                                 uint32_t n_cols, uint64_t* __restrict__ keys, uint32_t* __restrict__ col_state,
+                                                 unsigned long long* __restrict__ key_or) {
     __shared__ uint64_t tile[TC][TR + 1];
     const uint32_t tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -69,7 +71,7 @@ __global__ __launch_bounds__(256) void k_extract_columns(const int64_t* __restri
         for (uint32_t i = ty; i < TR; i += 8) {
             const uint64_t r = r0 + i;
             if (r < n && cb + tx < n_cols) {
-                const uint64_t cell = r * n_docs + c0 + cb + tx;
+                const uint64_t cell = row_of<BLOCK_HEADS>(lr, r) * n_docs + c0 + cb + tx;
                 const uint64_t v = (uint64_t)off[cell];
                 seen |= v;
                 tile[tx][i] = v | (st[cell] ? STRAND_BIT : 0ull);
@@ -84,7 +86,8 @@ __global__ __launch_bounds__(256) void k_extract_columns(const int64_t* __restri
                 const uint64_t key = tile[c][lane];
                 keys[(uint64_t)(cb + c) * n + r] = key;
                 if (r) {
-                    const uint64_t before = lane ? (tile[c][lane - 1] & ~STRAND_BIT) : (uint64_t)off[(r - 1) * n_docs + c0 + cb + c];
+                    const uint64_t before = lane ? (tile[c][lane - 1] & ~STRAND_BIT)
+                                                 : (uint64_t)off[row_of<BLOCK_HEADS>(lr, r - 1) * n_docs + c0 + cb + c];
                     descends = (key & ~STRAND_BIT) < before;
                 }
             }
@@ -96,14 +99,23 @@ __global__ __launch_bounds__(256) void k_extract_columns(const int64_t* __restri
     for (int o = 32; o >= 1; o >>= 1) seen |= __shfl_xor(seen, o, 64);
     if (lane == 0 && seen) atomicOr(key_or, (unsigned long long)seen);
 }
-void extract_columns(const int64_t* off, const uint8_t* st, uint32_t n, uint32_t n_docs, uint32_t c0, uint32_t n_cols,
-                     uint64_t* keys, uint32_t* col_state, uint64_t* key_or, hipStream_t s) {
+template <bool BLOCK_HEADS>
+static void extract(const int64_t* off, const uint8_t* st, const uint32_t* lr, uint32_t n, uint32_t n_docs, uint32_t c0,
+                    uint32_t n_cols, uint64_t* keys, uint32_t* col_state, uint64_t* key_or, hipStream_t s) {
     if (!n || !n_cols) return;
     const uint64_t tiles = ((uint64_t)n + TR - 1) / TR;
     const unsigned gx = (unsigned)(tiles < (1u << 18) ? tiles : (1u << 18)), gy = (n_cols + TC - 1) / TC;
-    hipLaunchKernelGGL(k_extract_columns, dim3(gx, gy), dim3(256), 0, s, off, st, n, n_docs, c0, n_cols, keys, col_state,
+    hipLaunchKernelGGL(k_extract<BLOCK_HEADS>, dim3(gx, gy), dim3(256), 0, s, off, st, lr, n, n_docs, c0, n_cols, keys, col_state,
                        reinterpret_cast<unsigned long long*>(key_or));
     MMT_HIP(hipGetLastError());
+}
+void extract_columns(const int64_t* off, const uint8_t* st, uint32_t n, uint32_t n_docs, uint32_t c0, uint32_t n_cols,
+                     uint64_t* keys, uint32_t* col_state, uint64_t* key_or, hipStream_t s) {
+    extract<false>(off, st, nullptr, n, n_docs, c0, n_cols, keys, col_state, key_or, s);
+}
+void extract_block_heads(const int64_t* off, const uint8_t* st, const uint32_t* lr, uint32_t n_blocks, uint32_t n_docs, uint32_t c0,
+                         uint32_t n_cols, uint64_t* keys, uint32_t* col_state, uint64_t* key_or, hipStream_t s) {
+    extract<true>(off, st, lr, n_blocks, n_docs, c0, n_cols, keys, col_state, key_or, s);
 }
 
 __global__ void k_iota(uint32_t* __restrict__ v, uint32_t n) {

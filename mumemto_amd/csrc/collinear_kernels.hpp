@@ -27,6 +27,9 @@ void anchor_keys(const int64_t* off, const uint32_t* rows, uint32_t m, uint32_t 
 // bit 63 set = a negative start).  col_state and key_or must be zero on entry.
 void extract_columns(const int64_t* off, const uint8_t* st, uint32_t n, uint32_t n_docs, uint32_t c0, uint32_t n_cols,
                      uint64_t* keys, uint32_t* col_state, uint64_t* key_or, hipStream_t s);
+// the same over the FIRST rows lr[2 b] of the n_blocks blocks: n_cols arrays of n_blocks keys (the inversion caller's block heads)
+void extract_block_heads(const int64_t* off, const uint8_t* st, const uint32_t* lr, uint32_t n_blocks, uint32_t n_docs, uint32_t c0,
+                         uint32_t n_cols, uint64_t* keys, uint32_t* col_state, uint64_t* key_or, hipStream_t s);
 void iota(uint32_t* v, uint32_t n, hipStream_t s);
 // One column: keys in ascending order of the start, perm[k] = row of keys[k] (null: the column was ascending already, the
 // identity).  Neighbours a = perm[k], b = perm[k + 1]: b == a + 1 and both '+' certify pair a, b == a - 1 and both '-' certify

@@ -11,26 +11,10 @@
 
 #include "coverage_kernels.hpp"
 #include "laps.hpp"
-#include "pool.hpp"
+#include "merged_tools.hpp"
 #include "prims.hpp"
 
 namespace mmt {
-namespace {
-
-int bit_width_u64(uint64_t v) { int b = 0; while (v) { b++; v >>= 1; } return b ? b : 1; }
-
-// room for `want` runs in m.d_runs; the first `have` runs stay
-void reserve_runs(MergedRows& m, size_t have, size_t want, hipStream_t st) {
-    if (want * 2 <= m.d_runs.size()) return;
-    DevBuf<int64_t> bigger;
-    bigger.ensure(std::max(want * 2, 2 * m.d_runs.size()));
-    if (have) MMT_HIP(hipMemcpyAsync(bigger.get(), m.d_runs.get(), have * 16, hipMemcpyDeviceToDevice, st));
-    MMT_HIP(hipStreamSynchronize(st));
-    m.d_runs.swap(bigger);
-}
-
-}  // namespace
-
 void coverage(Engine& e, MergedRows& m, const int64_t* seq_lengths, int64_t seq_idx, int64_t min_length, CoverageStats* stats) {
     if (m.n_rows > 0xffffffffull)
         throw std::invalid_argument("coverage: a table of 2^32 rows or more (" + std::to_string(m.n_rows) + ") is not supported");
@@ -54,50 +38,42 @@ void coverage(Engine& e, MergedRows& m, const int64_t* seq_lengths, int64_t seq_
     m.has_coverage = false;
     std::vector<uint64_t> covered(nd, 0), run_begin((size_t)nd + 1, 0);
     size_t n_runs = 0;
-    reserve_runs(m, 0, 1, st);
+    grow_keep(m.d_runs, 0, 2, st);
 
     if (n && first < last) {
         const uint32_t n_cols = last - first, tiles = cvk::scan_tiles(n);
         DevBuf<int64_t> d_len;
         DevBuf<uint64_t> begins, ends, sorted_b, sorted_e, tmax, carry, res;
-        DevBuf<uint32_t> heads, numbered, col_state;
+        DevBuf<uint32_t> heads, numbered;
+        ColumnFlags flags;
         d_len.ensure(nd);
         MMT_HIP(hipMemcpyAsync(d_len.get(), seq_lengths, (size_t)nd * 8, hipMemcpyHostToDevice, st));
         MMT_HIP(hipStreamSynchronize(st));
         sorted_b.ensure(n); sorted_e.ensure(n); heads.ensure(n); numbered.ensure(n);
         tmax.ensure(tiles); carry.ensure(tiles);
-        // the batch: as many columns of begins and ends as half of what the heap has free holds, beside the buffers of one column
-        size_t batch = n_cols;
-        const size_t avail = pool::available(e.device()) / 2, one_col = (size_t)n * 40;
-        if ((size_t)n_cols * n * 16 + one_col > avail) batch = avail > one_col ? (avail - one_col) / ((size_t)n * 16) : 1;
-        batch = (size_t)sw::num(sw::MMT_COLLINEAR_BATCH, batch);
-        batch = std::min<size_t>(std::max<size_t>(batch, 1), n_cols);
+        // columns of begins and ends, beside the buffers of one column
+        const size_t batch = columns_per_batch(e.device(), n_cols, (size_t)n * 16, (size_t)n * 40);
         begins.ensure(batch * n); ends.ensure(batch * n);
         // per column of the batch: covered positions, maximum of the ends (+ 1), run heads
         res.ensure(3 * batch);
-        // per column: 1 = not ascending; behind them, 8-byte aligned, the 64-bit OR of the begins and starts
-        const size_t or_at = (batch + 1) & ~(size_t)1;
-        col_state.ensure(or_at + 2);
-        std::vector<uint32_t> h_state(or_at + 2);
+        flags.ensure(batch);                         // (the OR is over the begins and the starts)
         for (uint32_t c0 = first; c0 < last; c0 += (uint32_t)batch) {
             const uint32_t cols = std::min<uint32_t>((uint32_t)batch, last - c0);
             laps.begin(0);
-            MMT_HIP(hipMemsetAsync(col_state.get(), 0, (or_at + 2) * 4, st));
+            flags.clear(st);
             MMT_HIP(hipMemsetAsync(res.get(), 0, 3 * batch * 8, st));
             cvk::extract_intervals(m.d_offsets.get(), m.d_length.get(), d_len.get(), n, nd, c0, cols, min_length, begins.get(),
-                                   ends.get(), col_state.get(), reinterpret_cast<uint64_t*>(col_state.get() + or_at), st);
+                                   ends.get(), flags.state(), flags.key_or_device(), st);
             laps.end();
-            MMT_HIP(hipMemcpyAsync(h_state.data(), col_state.get(), (or_at + 2) * 4, hipMemcpyDeviceToHost, st));
-            MMT_HIP(hipStreamSynchronize(st));
+            flags.read(st);
             laps.collect();
-            const uint64_t key_or = (uint64_t)h_state[or_at] | ((uint64_t)h_state[or_at + 1] << 32);
-            if (key_or >> 62) throw std::runtime_error("coverage: a start outside [-1, 2^62) in the table");
-            const int bits = bit_width_u64(key_or);
+            if (flags.key_or() >> 62) throw std::runtime_error("coverage: a start outside [-1, 2^62) in the table");
+            const int bits = bit_width_u64(flags.key_or());
             for (uint32_t c = 0; c < cols; c++) {
                 uint64_t* b = begins.get() + (size_t)c * n;
                 uint64_t* en = ends.get() + (size_t)c * n;
                 uint64_t* r = res.get() + 3 * (size_t)c;
-                if (h_state[c] & 1u) {
+                if (flags.descends(c)) {
                     laps.begin(1);
                     if (prims::sort_pairs_u64_u64_inplace(temp, b, sorted_b.get(), en, sorted_e.get(), n, 0, bits, st)) {
                         b = sorted_b.get(); en = sorted_e.get();
@@ -120,7 +96,7 @@ void coverage(Engine& e, MergedRows& m, const int64_t* seq_lengths, int64_t seq_
                 run_begin[c0 + c] = n_runs;
                 const size_t col_runs = (size_t)(h_res[2] & 0xffffffffull);
                 if (col_runs) {
-                    reserve_runs(m, n_runs, n_runs + col_runs, st);
+                    grow_keep(m.d_runs, 2 * n_runs, 2 * (n_runs + col_runs), st);
                     laps.begin(3);
                     prims::exclusive_sum_u32(temp, heads.get(), numbered.get(), n, st);
                     cvk::write_runs(b, en, heads.get(), numbered.get(), n, r + 1, m.d_runs.get() + 2 * n_runs, st);

@@ -61,6 +61,9 @@ public:
     DevBuf() = default;
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
+    // a move hands the allocation on as it is counted in DevBytes (or the borrowed view); the source is left empty
+    DevBuf(DevBuf&& o) noexcept { swap(o); }
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { release(); swap(o); } return *this; }
     ~DevBuf() { release(); }
     void ensure(size_t n) {
         if (n <= cap_) { n_ = n; return; }

@@ -23,14 +23,9 @@
 
 #include "device_utils.hpp"
 #include "guided_kernels.hpp"
+#include "launch_grid.hpp"
 
 namespace mmt { namespace gk {
-
-static inline unsigned grid_for(uint64_t items, unsigned per_block) {
-    uint64_t g = (items + per_block - 1) / per_block;
-    if (g >= (1ull << 24)) throw HipError("kernel launch of 2^32 work-items or more (" + std::to_string(items) + " items)");
-    return (unsigned)(g ? g : 1);
-}
 
 __device__ __forceinline__ uint64_t load_u64(const uint8_t* p) { uint64_t x; __builtin_memcpy(&x, p, 8); return x; }
 

@@ -11,28 +11,10 @@
 #include "collinear_kernels.hpp"
 #include "inversion_kernels.hpp"
 #include "laps.hpp"
-#include "pool.hpp"
+#include "merged_tools.hpp"
 #include "prims.hpp"
 
 namespace mmt {
-namespace {
-
-int bit_width_u64(uint64_t v) { int b = 0; while (v) { b++; v >>= 1; } return b ? b : 1; }
-
-// room for `want` records in m.d_calls; the first m.n_calls records stay
-void reserve_calls(MergedRows& m, size_t want, hipStream_t st) {
-    if (want * ik::CALL_FIELDS <= m.d_calls.size()) return;
-    DevBuf<int64_t> bigger;
-    bigger.ensure(std::max(want * ik::CALL_FIELDS, 2 * m.d_calls.size()));
-    if (m.n_calls) {
-        MMT_HIP(hipMemcpyAsync(bigger.get(), m.d_calls.get(), m.n_calls * ik::CALL_FIELDS * 8, hipMemcpyDeviceToDevice, st));
-        MMT_HIP(hipStreamSynchronize(st));
-    }
-    m.d_calls.swap(bigger);
-}
-
-}  // namespace
-
 void set_blocks(Engine& e, MergedRows& m, const uint32_t* lr, uint64_t n_blocks) {
     if (m.n_rows > 0xffffffffull)
         throw std::invalid_argument("set blocks: a table of 2^32 rows or more (" + std::to_string(m.n_rows) +
@@ -65,8 +47,7 @@ void set_blocks(Engine& e, MergedRows& m, const uint32_t* lr, uint64_t n_blocks)
     m.d_blocks.swap(blocks); m.d_row_block.swap(row_block);
     m.n_blocks = B;
     m.has_blocks = true;
-    m.has_calls = false; m.n_calls = 0;
-    m.has_bed = false;                           // (records of the blocks this call replaces)
+    m.blocks_replaced();
 }
 
 void inversion_calls(Engine& e, MergedRows& m, int64_t max_length, InversionStats* stats) {
@@ -82,46 +63,37 @@ void inversion_calls(Engine& e, MergedRows& m, int64_t max_length, InversionStat
     m.has_calls = false; m.n_calls = 0;
     const uint32_t B = (uint32_t)m.n_blocks, nd = (uint32_t)m.n_docs;
     S.blocks = B;
-    reserve_calls(m, 1, st);
+    grow_keep(m.d_calls, 0, ik::CALL_FIELDS, st);
 
     // a run is at least two blocks, and column 0 orders the blocks themselves
     if (B >= 2 && nd >= 2) {
         const uint32_t max_runs = B / 2;
         DevBuf<uint64_t> keys, sorted_keys;
-        DevBuf<uint32_t> blocks_in, order, col_state, plus, plus_sum, heads, tails, sel, count;
+        DevBuf<uint32_t> blocks_in, order, plus, plus_sum, heads, tails, sel, count;
         DevBuf<uint8_t> head, tail, keep;
         DevBuf<int64_t> rec;
+        ColumnFlags flags;
         sorted_keys.ensure(B); blocks_in.ensure(B); order.ensure(B);
         head.ensure(B); tail.ensure(B); plus.ensure(B); plus_sum.ensure(B);
         heads.ensure((size_t)B + 1); tails.ensure((size_t)B + 1); sel.ensure((size_t)max_runs + 1); keep.ensure((size_t)max_runs + 1);
         rec.ensure((size_t)max_runs * ik::CALL_FIELDS); count.ensure(4);
-        // the batch: as many columns of keys as half of what the heap has free holds, beside the buffers of one sort
-        const uint32_t n_cols = nd - 1;
-        size_t batch = n_cols;
-        const size_t avail = pool::available(e.device()) / 2, one_sort = (size_t)B * 24;
-        if ((size_t)n_cols * B * 8 + one_sort > avail) batch = avail > one_sort ? (avail - one_sort) / ((size_t)B * 8) : 1;
-        batch = (size_t)sw::num(sw::MMT_COLLINEAR_BATCH, batch);
-        batch = std::min<size_t>(std::max<size_t>(batch, 1), n_cols);
+        // columns of keys, beside the buffers of one sort
+        const size_t batch = columns_per_batch(e.device(), nd - 1, (size_t)B * 8, (size_t)B * 24);
         keys.ensure(batch * B);
-        // per column: 1 = not ascending; behind them, 8-byte aligned, the 64-bit OR of the starts
-        const size_t or_at = (batch + 1) & ~(size_t)1;
-        col_state.ensure(or_at + 2);
+        flags.ensure(batch);
         ck::iota(blocks_in.get(), B, st);
-        std::vector<uint32_t> h_state(or_at + 2);
         for (uint32_t c0 = 1; c0 < nd; c0 += (uint32_t)batch) {
             const uint32_t cols = std::min<uint32_t>((uint32_t)batch, nd - c0);
             laps.begin(0);
-            MMT_HIP(hipMemsetAsync(col_state.get(), 0, (or_at + 2) * 4, st));
-            ik::gather_heads(m.d_offsets.get(), m.d_strands.get(), m.d_blocks.get(), B, nd, c0, cols, keys.get(), col_state.get(),
-                             reinterpret_cast<uint64_t*>(col_state.get() + or_at), st);
+            flags.clear(st);
+            ck::extract_block_heads(m.d_offsets.get(), m.d_strands.get(), m.d_blocks.get(), B, nd, c0, cols, keys.get(),
+                                    flags.state(), flags.key_or_device(), st);
             laps.end();
-            MMT_HIP(hipMemcpyAsync(h_state.data(), col_state.get(), (or_at + 2) * 4, hipMemcpyDeviceToHost, st));
-            MMT_HIP(hipStreamSynchronize(st));
-            const uint64_t key_or = (uint64_t)h_state[or_at] | ((uint64_t)h_state[or_at + 1] << 32);
-            if (key_or >> 63) throw std::runtime_error("inversions: a negative start in the first row of a block");
-            const int bits = bit_width_u64(key_or);
+            flags.read(st);
+            if (flags.key_or() >> 63) throw std::runtime_error("inversions: a negative start in the first row of a block");
+            const int bits = bit_width_u64(flags.key_or());
             for (uint32_t c = 0; c < cols; c++) {
-                if (!(h_state[c] & 1u)) { S.cols_ascending++; continue; }      // the identity: every difference is +1
+                if (!flags.descends(c)) { S.cols_ascending++; continue; }      // the identity: every difference is +1
                 S.cols_sorted++;
                 laps.begin(1);
                 prims::sort_pairs_u64_u32(temp, keys.get() + (size_t)c * B, sorted_keys.get(), blocks_in.get(), order.get(), B, 0,
@@ -146,7 +118,7 @@ void inversion_calls(Engine& e, MergedRows& m, int64_t max_length, InversionStat
                     MMT_HIP(hipMemcpyAsync(&kept, count.get() + 2, 4, hipMemcpyDeviceToHost, st));
                     MMT_HIP(hipStreamSynchronize(st));
                     if (kept) {
-                        reserve_calls(m, m.n_calls + kept, st);
+                        grow_keep(m.d_calls, m.n_calls * ik::CALL_FIELDS, (m.n_calls + kept) * ik::CALL_FIELDS, st);
                         ik::compact(rec.get(), sel.get(), kept, m.d_calls.get() + m.n_calls * ik::CALL_FIELDS, st);
                         m.n_calls += kept;
                     }

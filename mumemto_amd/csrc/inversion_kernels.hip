@@ -5,14 +5,9 @@
 
 #include "device_utils.hpp"
 #include "inversion_kernels.hpp"
+#include "launch_grid.hpp"
 
 namespace mmt { namespace ik {
-
-// grid-stride kernels throughout: a launch stays far below 2^32 work-items for any count below 2^32
-static inline unsigned grid_capped(uint64_t items, unsigned per_block) {
-    const uint64_t g = (items + per_block - 1) / per_block;
-    return (unsigned)(g ? (g < (1ull << 20) ? g : (1ull << 20)) : 1);
-}
 
 __global__ void k_check_table(const int64_t* __restrict__ off, uint32_t n, uint32_t n_docs, uint32_t* __restrict__ state) {
     const uint64_t cells = (uint64_t)n * n_docs, stride = (uint64_t)gridDim.x * blockDim.x;
@@ -62,65 +57,6 @@ __global__ void k_rows_of_blocks(const uint32_t* __restrict__ lr, uint32_t n_blo
 void rows_of_blocks(const uint32_t* lr, uint32_t n_blocks, uint32_t n, uint32_t* row_block, hipStream_t s) {
     if (!n) return;
     hipLaunchKernelGGL(k_rows_of_blocks, dim3(grid_capped(n, 256)), dim3(256), 0, s, lr, n_blocks, n, row_block);
-    MMT_HIP(hipGetLastError());
-}
-
-// A tile is TR blocks x TC columns, as in extract_columns of collinear_kernels.hip, with the row of a block looked up in the
-// block list.  Read: the 32 lanes of a half-wave take 32 consecutive cells of one first row (256 contiguous bytes), 8 rows
-// per step.  Write: a wave takes 64 consecutive blocks of one column (512 contiguous bytes).  The LDS tile is [column][block]
-// with one key of padding per column.
-constexpr uint32_t TR = 64, TC = 32;
-
-__global__ __launch_bounds__(256) void k_gather_heads(const int64_t* __restrict__ off, const uint8_t* __restrict__ st,
-                                                      const uint32_t* __restrict__ lr, uint32_t n_blocks, uint32_t n_docs,
-                                                      uint32_t c0, uint32_t n_cols, uint64_t* __restrict__ keys,
-                                                      uint32_t* __restrict__ col_state, unsigned long long* __restrict__ key_or) {
-    __shared__ uint64_t tile[TC][TR + 1];
-    const uint32_t tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t cb = blockIdx.y * TC;
-    const uint32_t tiles = (uint32_t)(((uint64_t)n_blocks + TR - 1) / TR);
-    uint64_t seen = 0;
-    for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {
-        const uint64_t b0 = (uint64_t)t * TR;
-        for (uint32_t i = ty; i < TR; i += 8) {
-            const uint64_t b = b0 + i;
-            if (b < n_blocks && cb + tx < n_cols) {
-                const uint64_t cell = (uint64_t)lr[2 * b] * n_docs + c0 + cb + tx;
-                const uint64_t v = (uint64_t)off[cell];
-                seen |= v;
-                tile[tx][i] = v | (st[cell] ? STRAND_BIT : 0ull);
-            }
-        }
-        __syncthreads();
-        for (uint32_t c = wave; c < TC; c += 4) {
-            if (cb + c >= n_cols) break;                     // (uniform over the wave)
-            const uint64_t b = b0 + lane;
-            bool descends = false;
-            if (b < n_blocks) {
-                const uint64_t key = tile[c][lane];
-                keys[(uint64_t)(cb + c) * n_blocks + b] = key;
-                if (b) {
-                    const uint64_t before = lane ? (tile[c][lane - 1] & ~STRAND_BIT)
-                                                 : (uint64_t)off[(uint64_t)lr[2 * (b - 1)] * n_docs + c0 + cb + c];
-                    descends = (key & ~STRAND_BIT) < before;
-                }
-            }
-            if (__ballot(descends) != 0ull && lane == 0) atomicOr(&col_state[cb + c], 1u);
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) seen |= __shfl_xor(seen, o, 64);
-    if (lane == 0 && seen) atomicOr(key_or, (unsigned long long)seen);
-}
-void gather_heads(const int64_t* off, const uint8_t* st, const uint32_t* lr, uint32_t n_blocks, uint32_t n_docs, uint32_t c0,
-                  uint32_t n_cols, uint64_t* keys, uint32_t* col_state, uint64_t* key_or, hipStream_t s) {
-    if (!n_blocks || !n_cols) return;
-    const uint64_t tiles = ((uint64_t)n_blocks + TR - 1) / TR;
-    const unsigned gx = (unsigned)(tiles < (1u << 18) ? tiles : (1u << 18)), gy = (n_cols + TC - 1) / TC;
-    hipLaunchKernelGGL(k_gather_heads, dim3(gx, gy), dim3(256), 0, s, off, st, lr, n_blocks, n_docs, c0, n_cols, keys, col_state,
-                       reinterpret_cast<unsigned long long*>(key_or));
     MMT_HIP(hipGetLastError());
 }
 

@@ -25,11 +25,7 @@ void check_table(const int64_t* off, uint32_t n, uint32_t n_docs, uint32_t* stat
 void check_blocks(const uint32_t* lr, uint32_t n_blocks, uint32_t n, uint32_t* state, hipStream_t s);
 // row_block[i] = the block whose rows include i, or 0xFFFFFFFF (the blocks are ascending and disjoint)
 void rows_of_blocks(const uint32_t* lr, uint32_t n_blocks, uint32_t n, uint32_t* row_block, hipStream_t s);
-// Columns [c0, c0 + n_cols) of the FIRST rows of the blocks as n_cols arrays of n_blocks keys (start | strand << 63), through
-// a tile transpose in LDS: a first row is read n_cols x 8 contiguous bytes at a time, a column is written 64 keys at a time.
-// col_state[c - c0] |= 1 when the keys of column c are not non-decreasing; *key_or |= every start.  Both zero on entry.
-void gather_heads(const int64_t* off, const uint8_t* st, const uint32_t* lr, uint32_t n_blocks, uint32_t n_docs, uint32_t c0,
-                  uint32_t n_cols, uint64_t* keys, uint32_t* col_state, uint64_t* key_or, hipStream_t s);
+// (the keys of the block heads come from ck::extract_block_heads, collinear_kernels.hpp)
 // One column, n_blocks >= 2: order[j] = block at position j of the column, keys[j] its key.  dec[j] = order[j + 1] == order[j] - 1
 // (j + 1 < n_blocks); head[j] = dec[j] and not dec[j - 1]; tail[j] = dec[j] and not dec[j + 1]; plus[j] = strand of order[j].
 void mark(const uint32_t* order, const uint64_t* keys, uint32_t n_blocks, uint8_t* head, uint8_t* tail, uint32_t* plus,

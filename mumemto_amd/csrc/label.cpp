@@ -4,17 +4,15 @@
 #include "label.hpp"
 
 #include <algorithm>
-#include <chrono>
 #include <numeric>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
+#include "contig_table.hpp"
 #include "label_kernels.hpp"
 #include "laps.hpp"
-#include "piece_writer.hpp"
-#include "prims.hpp"
-#include "switches.hpp"
+#include "text_pieces.hpp"
 
 namespace mmt {
 namespace {
@@ -55,12 +53,7 @@ uint64_t measure_rows(Engine& e, const MergedRows& m, DevBuf<uint64_t>& offset) 
     bytes.ensure(n + 1); offset.ensure(n + 1);
     lk::measure(m.d_length.get(), m.d_offsets.get(), row_block(m), m.d_label_contig.get(), m.d_label_rel.get(), (uint32_t)n,
                 (uint32_t)m.n_docs, m.d_label_contig_begin.get(), m.label_names ? m.d_label_name_begin.get() : nullptr, bytes.get(), st);
-    MMT_HIP(hipMemsetAsync(bytes.get() + n, 0, 8, st));
-    prims::exclusive_sum_u64(e.scratch(), bytes.get(), offset.get(), n + 1, st);
-    uint64_t total = 0;
-    MMT_HIP(hipMemcpyAsync(&total, offset.get() + n, 8, hipMemcpyDeviceToHost, st));
-    MMT_HIP(hipStreamSynchronize(st));
-    return total;
+    return line_offsets(e.scratch(), bytes.get(), offset.get(), n, st);
 }
 
 // the lines of rows [r0, r1) at text[0 ..)
@@ -82,47 +75,17 @@ void label(Engine& e, MergedRows& m, const uint64_t* contig_begin, const int64_t
     if (m.n_rows > 0xffffffffull)
         throw std::invalid_argument("label: a table of 2^32 rows or more (" + std::to_string(m.n_rows) + ") is not supported");
     if (m.n_docs > 0xffffffffull || (m.n_rows && !m.n_docs)) throw std::invalid_argument("label: the table has no columns");
-    if (!contig_begin) throw std::invalid_argument("label: contig_begin must hold n_docs + 1 entries");
     const uint32_t nd = (uint32_t)m.n_docs, n = (uint32_t)m.n_rows;
-    for (uint32_t c = 0; c < nd; c++)
-        if (contig_begin[c] > contig_begin[c + 1]) throw std::invalid_argument("label: contig_begin does not ascend");
-    const uint64_t n_contigs = contig_begin[nd];
-    if (n_contigs && !contig_len) throw std::invalid_argument("label: contig_len must hold an entry per contig");
-    if (use_names && !name_begin) throw std::invalid_argument("label: name_begin must hold an entry per contig and one more");
-    uint64_t name_bytes = 0;
-    if (use_names) {
-        for (uint64_t g = 0; g < n_contigs; g++)
-            if (name_begin[g] > name_begin[g + 1]) throw std::invalid_argument("label: name_begin does not ascend");
-        name_bytes = n_contigs ? name_begin[n_contigs] : 0;
-        if (name_bytes && !names) throw std::invalid_argument("label: names must hold the bytes name_begin refers to");
-    }
-    // cumulative lengths per column; every column is needed
-    std::vector<int64_t> ends((size_t)n_contigs + 1, 0), totals(nd, 0);
+    // every column is needed
+    const ContigTable table = check_contig_table({"label", 0, nd, true, use_names, "\t\n,", "a start"}, nd, contig_begin, contig_len,
+                                                 name_begin, names);
+    const uint64_t n_contigs = table.n_contigs, name_bytes = table.name_bytes;
+    const std::vector<int64_t>& totals = table.totals;
     uint64_t longest_line = 0;
     for (uint32_t c = 0; c < nd; c++) {
-        if (contig_begin[c] == contig_begin[c + 1])
-            throw std::invalid_argument("label: sequence " + std::to_string(c) + " has no contigs");
         if (contig_begin[c + 1] - contig_begin[c] > 0xfffffffeull)
             throw std::invalid_argument("label: sequence " + std::to_string(c) + " has 2^32 contigs or more");
-        uint64_t run = 0, longest_name = 0;
-        for (uint64_t g = contig_begin[c]; g < contig_begin[c + 1]; g++) {
-            if (contig_len[g] < 0)
-                throw std::invalid_argument("label: contig " + std::to_string(g - contig_begin[c]) + " of sequence " + std::to_string(c) +
-                                            " has the negative length " + std::to_string(contig_len[g]));
-            run += (uint64_t)contig_len[g];
-            if (run >> 62) throw std::invalid_argument("label: sequence " + std::to_string(c) + " is 2^62 bases or longer");
-            ends[g] = (int64_t)run;
-            if (!use_names) continue;
-            longest_name = std::max<uint64_t>(longest_name, name_begin[g + 1] - name_begin[g]);
-            for (uint64_t i = name_begin[g]; i < name_begin[g + 1]; i++)
-                if (names[i] == '\t' || names[i] == '\n' || names[i] == ',')
-                    throw std::invalid_argument("label: the name of contig " + std::to_string(g - contig_begin[c]) + " of sequence " +
-                                                std::to_string(c) + " contains a tab, a newline or a comma");
-        }
-        if (run == 0)
-            throw std::invalid_argument("label: sequence " + std::to_string(c) + " has total length 0: no contig can hold a start");
-        totals[c] = (int64_t)run;
-        longest_line += longest_name + 64;
+        longest_line += table.longest_name[c] + 64;
     }
     if (longest_line >> 31) throw std::invalid_argument("label: a line of 2^31 bytes or more (names of " + std::to_string(longest_line) + " bytes)");
     hipStream_t st = e.stream();
@@ -141,7 +104,7 @@ void label(Engine& e, MergedRows& m, const uint64_t* contig_begin, const int64_t
     m.d_label_contig_begin.ensure((size_t)nd + 1);
     m.d_label_name_begin.ensure((size_t)n_contigs + 1); m.d_label_names.ensure((size_t)name_bytes + 1);
     m.d_label_contig.ensure(cells + 1); m.d_label_rel.ensure(cells + 1);
-    MMT_HIP(hipMemcpyAsync(d_ends.get(), ends.data(), ((size_t)n_contigs + 1) * 8, hipMemcpyHostToDevice, st));
+    MMT_HIP(hipMemcpyAsync(d_ends.get(), table.ends.data(), ((size_t)n_contigs + 1) * 8, hipMemcpyHostToDevice, st));
     if (nd) MMT_HIP(hipMemcpyAsync(d_plan.get(), plan.data(), (size_t)nd * 4, hipMemcpyHostToDevice, st));
     MMT_HIP(hipMemcpyAsync(m.d_label_contig_begin.get(), contig_begin, ((size_t)nd + 1) * 8, hipMemcpyHostToDevice, st));
     if (use_names && n_contigs)
@@ -212,62 +175,13 @@ void label_write_text(Engine& e, const MergedRows& m, const std::string& path, L
     hipStream_t st = e.stream();
     MMT_HIP(hipSetDevice(e.device()));
     Laps laps(st, stats ? stats->ms : nullptr);
-    const size_t n = m.n_rows;
-    size_t piece_bytes = LABEL_TEXT_PIECE;
-    if (sw::is_set(sw::MMT_MERGED_TEXT_PIECE)) piece_bytes = std::max<size_t>(sw::num(sw::MMT_MERGED_TEXT_PIECE, 0), 4096);
     DevBuf<uint64_t> offset;
     laps.begin(1);
     const uint64_t bytes = measure_rows(e, m, offset);
     laps.end();
-    std::vector<size_t> cut(1, 0);
-    std::vector<uint64_t> h_off;
-    uint64_t longest = 0;
-    const bool one = bytes <= piece_bytes;
-    if (one) {
-        if (bytes) cut.push_back(n);
-        longest = bytes;
-    } else {
-        h_off.resize(n + 1);
-        MMT_HIP(hipMemcpyAsync(h_off.data(), offset.get(), (n + 1) * 8, hipMemcpyDeviceToHost, st));
-        MMT_HIP(hipStreamSynchronize(st));
-        for (size_t r = 0; r < n;) {
-            const uint64_t lim = h_off[r] + piece_bytes;
-            size_t q = (size_t)(std::upper_bound(h_off.begin() + r + 1, h_off.end(), lim) - h_off.begin()) - 1;
-            if (q <= r) q = r + 1;
-            longest = std::max<uint64_t>(longest, h_off[q] - h_off[r]);
-            cut.push_back(q);
-            r = q;
-        }
-    }
-    DevBuf<char> d_piece[2];
-    for (auto& d : d_piece) d.ensure((size_t)longest + 1);
-    double wait_ms = 0;
-    auto waited = [&wait_ms](std::chrono::steady_clock::time_point t0) {
-        wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    };
-    PieceWriter writer((size_t)longest + 1, 2);
-    writer.open(path, e.device(), false);        // (left open by an exception: its destructor removes PATH.tmp)
-    for (size_t i = 0; i + 1 < cut.size(); i++) {
-        DevBuf<char>& d = d_piece[i & 1];
-        const size_t r0 = cut[i], r1 = cut[i + 1];
-        const uint64_t from = one ? 0 : h_off[r0], to = one ? bytes : h_off[r1];
-        auto t0 = std::chrono::steady_clock::now();
-        PieceWriter::Piece pc = writer.room((size_t)(to - from));
-        waited(t0);
-        laps.begin(2);
-        write_rows(e, m, offset, r0, r1, from, d.get());
-        laps.end();
-        laps.begin(3);
-        MMT_HIP(hipMemcpyAsync(pc.p, d.get(), pc.n, hipMemcpyDeviceToHost, st));
-        laps.end();
-        MMT_HIP(hipStreamSynchronize(st));
-        writer.push(pc);
-    }
-    MMT_HIP(hipStreamSynchronize(st));
-    laps.collect();
-    auto t0 = std::chrono::steady_clock::now();
-    writer.close();
-    waited(t0);
+    const double wait_ms = write_text_pieces(
+        st, e.device(), offset.get(), m.n_rows, bytes, text_piece_bytes(LABEL_TEXT_PIECE), path,
+        [&](size_t r0, size_t r1, uint64_t base, char* dst) { write_rows(e, m, offset, r0, r1, base, dst); }, {&laps, 2, 3});
     if (stats) { stats->ms[3] += (float)wait_ms; stats->text_bytes = bytes; }
 }
 

@@ -5,26 +5,14 @@
 
 #include "device_utils.hpp"
 #include "label_kernels.hpp"
+#include "launch_grid.hpp"
+#include "table_text.hpp"
 
 namespace mmt { namespace lk {
 
-// grid-stride kernels throughout: a launch stays far below 2^32 work-items for any count below 2^32
-static inline unsigned grid_capped(uint64_t items, unsigned per_block, uint64_t cap = 1ull << 20) {
-    const uint64_t g = (items + per_block - 1) / per_block;
-    return (unsigned)(g ? (g < cap ? g : cap) : 1);
-}
+using namespace tt;      // the decimals, wave sums, field writers and the contig search
 
 // ---- contig lookup --------------------------------------------------------------------------------------------------------
-// the first i in [0, cnt) with ends[i] > v, cnt when there is none
-__device__ __forceinline__ uint32_t upper_bound(const int64_t* ends, uint32_t cnt, int64_t v) {
-    uint32_t lo = 0, hi = cnt;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (ends[mid] > v) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(LABEL_BLOCK) void k_lookup(const int64_t* __restrict__ off, uint32_t n, uint32_t n_docs, uint64_t row0,
                                                         const uint64_t* __restrict__ contig_begin,
                                                         const int64_t* __restrict__ ends, const uint32_t* __restrict__ stage_at,
@@ -110,30 +98,6 @@ void lookup(const int64_t* off, uint32_t n, uint32_t n_docs, uint64_t row0, cons
 }
 
 // ---- text -----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t ndigits(uint64_t v) {
-    uint32_t d = 1;
-    while (v >= 10) { v /= 10; d++; }
-    return d;
-}
-__device__ __forceinline__ void put_uint(char* dst, uint64_t v, uint32_t nd) {
-    for (uint32_t i = nd; i-- > 0;) { dst[i] = (char)('0' + v % 10); v /= 10; }
-}
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_excl_sum(uint32_t v, uint32_t lane, uint32_t& total) {
-    uint32_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { uint32_t y = __shfl_up(x, o, 64); if (lane >= (uint32_t)o) x += y; }
-    total = __shfl(x, 63, 64);
-    return x - v;
-}
-// width of one cell: optional '-' + digits of |v|
-__device__ __forceinline__ uint32_t cell_width(int64_t v) {
-    return v < 0 ? 1u + ndigits(0ull - (uint64_t)v) : ndigits((uint64_t)v);
-}
 // the fourth field: * without blocks, the row's block, or - for none
 __device__ __forceinline__ uint32_t block_width(const uint32_t* __restrict__ block, uint64_t r) {
     return !block || block[r] == NO_BLOCK ? 1u : ndigits(block[r]);
@@ -152,7 +116,7 @@ __global__ __launch_bounds__(TEXT_BLOCK) void k_measure(const uint32_t* __restri
         uint32_t w = 0;
         for (uint32_t d = lane; d < n_docs; d += 64) {
             const uint64_t cell = r * n_docs + d;
-            w += cell_width(off[cell]) + cell_width(rel[cell]);
+            w += int_width(off[cell]) + int_width(rel[cell]);
             if (name_begin) {
                 const uint64_t g = contig_begin[d] + contig[cell];
                 w += (uint32_t)(name_begin[g + 1] - name_begin[g]);
@@ -173,25 +137,6 @@ void measure(const uint32_t* len, const int64_t* off, const uint32_t* block, con
     hipLaunchKernelGGL(k_measure, dim3(grid_capped(n, TEXT_WAVES)), dim3(TEXT_BLOCK), 0, s, len, off, block, contig, rel, n, n_docs,
                        contig_begin, name_begin, bytes);
     MMT_HIP(hipGetLastError());
-}
-
-// a field of decimals separated by commas at t + cur, one cell per lane and 64 cells per step; returns where the field ends
-template <typename T>
-__device__ __forceinline__ uint32_t put_numbers(char* t, uint32_t cur, const T* __restrict__ row, uint32_t n_docs, uint32_t lane) {
-    for (uint32_t base = 0; base < n_docs; base += 64) {
-        const uint32_t d = base + lane;
-        int64_t v = 0; uint32_t cw = 0, wd = 0;
-        if (d < n_docs) { v = (int64_t)row[d]; cw = cell_width(v); wd = cw + (d + 1 < n_docs ? 1 : 0); }
-        uint32_t total;
-        const uint32_t at = wave_excl_sum(wd, lane, total);
-        if (d < n_docs) {
-            char* c = t + cur + at;
-            if (v < 0) { c[0] = '-'; put_uint(c + 1, 0ull - (uint64_t)v, cw - 1); } else put_uint(c, (uint64_t)v, cw);
-            if (d + 1 < n_docs) c[cw] = ',';
-        }
-        cur += total;
-    }
-    return cur;
 }
 
 // the names of the row's contigs separated by commas: per 64 cells a prefix sum places the names, then the bytes of the
@@ -246,12 +191,7 @@ __global__ __launch_bounds__(TEXT_BLOCK) void k_write_lines(const uint32_t* __re
         if (lane == 0) { put_uint(t, len[r], nl); t[nl] = '\t'; }
         uint32_t cur = put_numbers(t, nl + 1, off + r * n_docs, n_docs, lane);
         if (lane == 0) t[cur] = '\t';
-        cur += 1;
-        for (uint32_t d = lane; d < n_docs; d += 64) {
-            t[cur + 2 * d] = st[r * n_docs + d] ? '+' : '-';
-            if (d + 1 < n_docs) t[cur + 2 * d + 1] = ',';
-        }
-        cur += 2 * n_docs - 1;
+        cur = put_strands(t, cur + 1, st + r * n_docs, n_docs, lane);
         const uint32_t bw = block_width(block, r);
         if (lane == 0) {
             t[cur] = '\t';

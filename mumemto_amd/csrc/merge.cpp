@@ -16,9 +16,9 @@
 
 #include "kernels.hpp"
 #include "merge_kernels.hpp"
-#include "piece_writer.hpp"
 #include "pfp_kernels.hpp"
 #include "prims.hpp"
+#include "text_pieces.hpp"
 
 namespace mmt {
 namespace {
@@ -453,11 +453,7 @@ void sort_like_direct(Engine& e, MergedRows& m) {
     if (bad) throw std::runtime_error("anchor offset outside the anchor");
     m.d_length.swap(len2); m.d_offsets.swap(off2); m.d_strands.swap(st2);
     m.on_host = false;
-    m.has_blocks = false; m.n_blocks = 0;       // (blocks are row ranges of the order they were computed in)
-    m.has_calls = false; m.n_calls = 0;
-    m.has_coverage = false;
-    m.has_bed = false;
-    m.has_label = false;
+    m.table_replaced();                          // (blocks are row ranges of the order they were computed in)
 }
 
 // the fourth field of the text: the collinear block of every row, when blocks are attached (collinear.hpp)
@@ -517,8 +513,6 @@ void write_merged_text(Engine& e, const MergedRows& m, const std::string& path) 
     const size_t n = m.n_rows;
     hipStream_t st = e.stream();
     MMT_HIP(hipSetDevice(e.device()));
-    size_t piece_bytes = MERGED_TEXT_PIECE;
-    if (sw::is_set(sw::MMT_MERGED_TEXT_PIECE)) piece_bytes = std::max<size_t>(sw::num(sw::MMT_MERGED_TEXT_PIECE, 0), 4096);
     // ~ (digits + comma + strand + comma) per cell: an upper bound good enough to choose the route
     const bool one_piece = !sw::is_set(sw::MMT_MERGED_TEXT_PIECE) && (double)n * (double)m.n_docs * 24.0 < (double)MERGED_TEXT_ONE_PIECE;
     if (!n || one_piece) {
@@ -530,38 +524,14 @@ void write_merged_text(Engine& e, const MergedRows& m, const std::string& path) 
     DevBuf<uint64_t> tlen, toff;
     tlen.ensure(n + 1); toff.ensure(n + 1);
     mk::table_measure(m.d_length.get(), m.d_offsets.get(), row_block(m), (uint32_t)n, (uint32_t)m.n_docs, tlen.get(), st);
-    MMT_HIP(hipMemsetAsync(tlen.get() + n, 0, 8, st));
-    prims::exclusive_sum_u64(e.scratch(), tlen.get(), toff.get(), n + 1, st);     // toff[n] = all bytes
-    std::vector<uint64_t> h_off(n + 1);
-    MMT_HIP(hipMemcpyAsync(h_off.data(), toff.get(), (n + 1) * 8, hipMemcpyDeviceToHost, st));
-    MMT_HIP(hipStreamSynchronize(st));
+    const uint64_t bytes = line_offsets(e.scratch(), tlen.get(), toff.get(), n, st);
     tlen.release();
-    // pieces of whole rows, each at most piece_bytes (a single row longer than that is a piece of its own)
-    std::vector<size_t> cut(1, 0);
-    uint64_t longest = 0;
-    for (size_t r = 0; r < n;) {
-        const uint64_t lim = h_off[r] + piece_bytes;
-        size_t q = (size_t)(std::upper_bound(h_off.begin() + r + 1, h_off.end(), lim) - h_off.begin()) - 1;
-        if (q <= r) q = r + 1;
-        longest = std::max<uint64_t>(longest, h_off[q] - h_off[r]);
-        cut.push_back(q);
-        r = q;
-    }
-    DevBuf<char> d_piece[2];
-    for (auto& d : d_piece) d.ensure(longest + 1);
-    PieceWriter writer(longest + 1, 2);
-    writer.open(path, e.device(), false);        // (left open by an exception: its destructor removes PATH.tmp)
-    for (size_t i = 0; i + 1 < cut.size(); i++) {
-        DevBuf<char>& d = d_piece[i & 1];
-        const size_t r0 = cut[i], r1 = cut[i + 1];
-        PieceWriter::Piece pc = writer.room(h_off[r1] - h_off[r0]);
-        mk::table_write(m.d_length.get() + r0, m.d_offsets.get() + r0 * m.n_docs, m.d_strands.get() + r0 * m.n_docs,
-                        row_block(m) ? row_block(m) + r0 : nullptr, (uint32_t)(r1 - r0), (uint32_t)m.n_docs, toff.get() + r0, h_off[r0], d.get(), st);
-        MMT_HIP(hipMemcpyAsync(pc.p, d.get(), pc.n, hipMemcpyDeviceToHost, st));
-        MMT_HIP(hipStreamSynchronize(st));
-        writer.push(pc);
-    }
-    writer.close();
+    write_text_pieces(st, e.device(), toff.get(), n, bytes, text_piece_bytes(MERGED_TEXT_PIECE), path,
+                      [&](size_t r0, size_t r1, uint64_t base, char* dst) {
+                          mk::table_write(m.d_length.get() + r0, m.d_offsets.get() + r0 * m.n_docs, m.d_strands.get() + r0 * m.n_docs,
+                                          row_block(m) ? row_block(m) + r0 : nullptr, (uint32_t)(r1 - r0), (uint32_t)m.n_docs,
+                                          toff.get() + r0, base, dst, st);
+                      });
 }
 
 void download_merged(Engine& e, MergedRows& m) {

@@ -6,24 +6,13 @@
 #include <string>
 
 #include "device_utils.hpp"
+#include "launch_grid.hpp"
 #include "merge_kernels.hpp"
+#include "table_text.hpp"
 
 namespace mmt { namespace mk {
 
-// A launch may not have 2^32 work-items or more (HIP folds the product of grid and workgroup size into 32 bits: a
-// larger launch silently runs a fraction of its workgroups).  Every kernel here uses workgroups of at most 256
-// work-items with grid_for, so 2^24 workgroups is the limit; kernels over text-sized ranges handle 4 - 16 items per
-// work-item and stay below it for any text that fits the device.
-static inline unsigned grid_for(uint64_t items, unsigned per_block) {
-    uint64_t g = (items + per_block - 1) / per_block;
-    if (g >= (1ull << 24)) throw HipError("kernel launch of 2^32 work-items or more (" + std::to_string(items) + " items)");
-    return (unsigned)(g ? g : 1);
-}
-// for grid-stride kernels
-static inline unsigned grid_capped(uint64_t items, unsigned per_block) {
-    const uint64_t g = (items + per_block - 1) / per_block;
-    return (unsigned)(g ? (g < (1ull << 20) ? g : (1ull << 20)) : 1);
-}
+using namespace tt;      // the decimals, wave sums and field writers of the table text
 
 __global__ void k_leaf_keys(const int64_t* __restrict__ offsets, uint32_t n_rows, uint32_t n_docs, uint64_t L,
                             uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t* __restrict__ bad) {
@@ -204,30 +193,6 @@ void rank_keys(const int64_t* off, uint32_t n, uint32_t n_docs, const uint32_t* 
 }
 
 // ---- text ------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t ndigits(uint64_t v) {
-    uint32_t d = 1;
-    while (v >= 10) { v /= 10; d++; }
-    return d;
-}
-__device__ __forceinline__ void put_uint(char* dst, uint64_t v, uint32_t nd) {
-    for (uint32_t i = nd; i-- > 0;) { dst[i] = (char)('0' + v % 10); v /= 10; }
-}
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_excl_sum(uint32_t v, uint32_t lane, uint32_t& total) {
-    uint32_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { uint32_t y = __shfl_up(x, o, 64); if (lane >= (uint32_t)o) x += y; }
-    total = __shfl(x, 63, 64);
-    return x - v;
-}
-// width of one offsets cell: optional '-' + digits of |o|
-__device__ __forceinline__ uint32_t cell_width(int64_t o) {
-    return o < 0 ? 1u + ndigits((uint64_t)(-o)) : ndigits((uint64_t)o);
-}
 
 // the optional fourth field (collinear block of the row, mumemto/utils.py:637-653): \t + its number, or \t- for none
 __device__ __forceinline__ uint32_t block_width(const uint32_t* __restrict__ block, uint64_t r) {
@@ -241,7 +206,7 @@ __global__ void k_table_measure(const uint32_t* __restrict__ len, const int64_t*
     const uint32_t lane = threadIdx.x & 63;
     if (r >= n) return;
     uint32_t w = 0;
-    for (uint32_t d = lane; d < n_docs; d += 64) w += cell_width(off[r * n_docs + d]);
+    for (uint32_t d = lane; d < n_docs; d += 64) w += int_width(off[r * n_docs + d]);
     w = wave_sum(w);
     // LEN \t offs(N-1 commas) \t strands(N chars, N-1 commas) [\t block] \n
     if (lane == 0)
@@ -265,28 +230,10 @@ __global__ void k_table_write(const uint32_t* __restrict__ len, const int64_t* _
     char* t = text + (text_off[r] - text_base);
     const uint32_t nl = ndigits(len[r]);
     if (lane == 0) { put_uint(t, len[r], nl); t[nl] = '\t'; }
-    uint32_t cur = nl + 1;
-    for (uint32_t base = 0; base < n_docs; base += 64) {
-        const uint32_t d = base + lane;
-        int64_t o = 0; uint32_t cw = 0, wd = 0;
-        if (d < n_docs) { o = off[r * n_docs + d]; cw = cell_width(o); wd = cw + (d + 1 < n_docs ? 1 : 0); }
-        uint32_t total;
-        const uint32_t at = wave_excl_sum(wd, lane, total);
-        if (d < n_docs) {
-            char* c = t + cur + at;
-            if (o < 0) { c[0] = '-'; put_uint(c + 1, (uint64_t)(-o), cw - 1); } else put_uint(c, (uint64_t)o, cw);
-            if (d + 1 < n_docs) c[cw] = ',';
-        }
-        cur += total;
-    }
+    uint32_t cur = put_numbers(t, nl + 1, off + r * n_docs, n_docs, lane);
     if (lane == 0) t[cur] = '\t';
-    cur += 1;
-    for (uint32_t d = lane; d < n_docs; d += 64) {
-        t[cur + 2 * d] = st[r * n_docs + d] ? '+' : '-';
-        if (d + 1 < n_docs) t[cur + 2 * d + 1] = ',';
-    }
+    cur = put_strands(t, cur + 1, st + r * n_docs, n_docs, lane);
     if (lane == 0) {
-        cur += 2 * n_docs - 1;
         if (block) {
             t[cur++] = '\t';
             const uint32_t b = block[r];

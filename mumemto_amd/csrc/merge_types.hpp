@@ -2,6 +2,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <utility>
 #include <vector>
 
 #include "device_utils.hpp"
@@ -52,29 +53,15 @@ struct MergedRows {
     DevBuf<char> d_label_names;
 
     MergedRows() = default;
-    MergedRows(MergedRows&& o) noexcept { *this = std::move(o); }
-    MergedRows& operator=(MergedRows&& o) noexcept {
-        n_docs = o.n_docs; n_rows = o.n_rows; thresh_len = o.thresh_len; on_host = o.on_host;
-        d_length.swap(o.d_length); d_offsets.swap(o.d_offsets); d_strands.swap(o.d_strands); d_thresh.swap(o.d_thresh);
-        length = std::move(o.length); offsets = std::move(o.offsets); strands = std::move(o.strands);
-        thresh = std::move(o.thresh);
-        has_blocks = o.has_blocks; n_blocks = o.n_blocks;
-        d_row_block.swap(o.d_row_block); d_blocks.swap(o.d_blocks);
-        has_calls = o.has_calls; n_calls = o.n_calls;
-        d_calls.swap(o.d_calls);
-        has_coverage = o.has_coverage;
-        cov_covered = std::move(o.cov_covered); cov_run_begin = std::move(o.cov_run_begin);
-        d_run_begin.swap(o.d_run_begin); d_runs.swap(o.d_runs);
-        has_bed = o.has_bed;
-        bed_record_begin = std::move(o.bed_record_begin); bed_contig_begin = std::move(o.bed_contig_begin);
-        d_bed_record_begin.swap(o.d_bed_record_begin); d_bed_records.swap(o.d_bed_records);
-        d_bed_name_begin.swap(o.d_bed_name_begin); d_bed_names.swap(o.d_bed_names);
-        has_label = o.has_label; label_names = o.label_names;
-        d_label_contig.swap(o.d_label_contig); d_label_rel.swap(o.d_label_rel);
-        d_label_contig_begin.swap(o.d_label_contig_begin); d_label_name_begin.swap(o.d_label_name_begin);
-        d_label_names.swap(o.d_label_names);
-        return *this;
-    }
+    MergedRows(MergedRows&&) noexcept = default;
+    MergedRows& operator=(MergedRows&&) noexcept = default;
+
+    // Which results go when something they read is replaced -- the one place that says so.  Blocks, calls and BED records are
+    // row ranges and readings of the blocks; coverage and labels read the table alone.  (A tool clears its OWN flag on entry.)
+    // new blocks (collinear_blocks, set_blocks): calls and BED records go, coverage and labels stay
+    void blocks_replaced() { has_calls = false; n_calls = 0; has_bed = false; }
+    // a new table or row order (sort_like_direct, collinear_blocks): everything attached goes
+    void table_replaced() { has_blocks = false; n_blocks = 0; blocks_replaced(); has_coverage = false; has_label = false; }
 };
 
 }  // namespace mmt

@@ -10,6 +10,7 @@
 
 #include "device_utils.hpp"
 #include "kernels.hpp"
+#include "launch_grid.hpp"
 #include "parse_lcp.hpp"
 #include "prims.hpp"
 #include "wide.hpp"
@@ -17,12 +18,6 @@
 namespace mmt {
 
 namespace {
-
-inline unsigned grid_for(uint64_t items, unsigned per_block) {
-    uint64_t g = (items + per_block - 1) / per_block;
-    if (g >= (1ull << 24)) throw HipError("kernel launch of 2^32 work-items or more (" + std::to_string(items) + " items)");
-    return (unsigned)(g ? g : 1);
-}
 
 
 // Irreducible entries of the parse's suffix array: the phrase before sa_p[r] differs from the phrase before sa_p[r - 1]

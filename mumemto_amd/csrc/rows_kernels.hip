@@ -12,50 +12,19 @@
 #include <string>
 
 #include "device_utils.hpp"
+#include "launch_grid.hpp"
 #include "rows_kernels.hpp"
+#include "table_text.hpp"
 #include "textref.hpp"
 
 namespace mmt { namespace rk {
 
-// A launch may not have 2^32 work-items or more (HIP folds the product of grid and workgroup size into 32 bits: a
-// larger launch silently runs a fraction of its workgroups).  Every kernel here uses workgroups of at most 256
-// work-items with grid_for, so 2^24 workgroups is the limit; kernels over text-sized ranges handle 4 - 16 items per
-// work-item and stay below it for any text that fits the device.
-static inline unsigned grid_for(uint64_t items, unsigned per_block) {
-    uint64_t g = (items + per_block - 1) / per_block;
-    if (g >= (1ull << 24)) throw HipError("kernel launch of 2^32 work-items or more (" + std::to_string(items) + " items)");
-    return (unsigned)(g ? g : 1);
-}
+using namespace tt;      // ndigits, put_uint, wave_sum, wave_min, wave_excl_sum
 
 __device__ __forceinline__ uint32_t doc_lookup(const uint64_t* __restrict__ start, uint32_t n_docs, uint64_t p) {
     uint32_t lo = 0, hi = n_docs;
     while (lo < hi) { uint32_t mid = (lo + hi + 1) >> 1; if (start[mid] <= p) lo = mid; else hi = mid - 1; }
     return lo;
-}
-__device__ __forceinline__ uint32_t ndigits(uint64_t v) {
-    uint32_t d = 1;
-    while (v >= 10) { v /= 10; d++; }
-    return d;
-}
-__device__ __forceinline__ void put_uint(char* dst, uint64_t v, uint32_t nd) {
-    for (uint32_t i = nd; i-- > 0;) { dst[i] = (char)('0' + v % 10); v /= 10; }
-}
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { uint32_t w = __shfl_xor(v, o, 64); v = w < v ? w : v; }
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_excl_sum(uint32_t v, uint32_t lane, uint32_t& total) {
-    uint32_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { uint32_t y = __shfl_up(x, o, 64); if (lane >= (uint32_t)o) x += y; }
-    total = __shfl(x, 63, 64);
-    return x - v;
 }
 
 // key for the pop order of the reference's stack: closing position ascending, longer first

@@ -324,6 +324,42 @@ def test_refusals(engine):
         assert engine.L.mmt_merged_bed_write_text(m.h, -1, b"/dev/null") == 3
 
 
+def test_a_column_written_in_pieces_is_the_column_written_whole(engine, tmp_path):
+    """bed_write_text cuts a column into pieces of whole lines (MMT_MERGED_TEXT_PIECE is the test hook; 256 MB otherwise): two
+    columns of 402 records, in column 1 a contig whose name alone is longer than a piece, so that its lines are pieces of
+    their own; the files equal bed_text with the hook and without it"""
+    import mumemto_amd
+    t = M.make_rows(77, 1400, 2)
+    blocks = M.make_blocks(78, 1400)
+    names, lens = M.make_contigs(79, t[3], [3, 40])
+    want = M.bed(t[0], t[1], t[2], (names, lens), None, 100, blocks)
+    assert want[0].tolist() == [0, 402, 804]
+    middle = int(want[1][402 + 201][0])                       # the contig of a record in the middle of column 1
+    names = [list(names[0]), list(names[1])]
+    names[1][middle] = "contig_" + "n" * 5000
+    contigs = (names, lens)
+    with mumemto_amd.Merged.from_rows(engine, *t[:3]) as m:
+        m.set_blocks(blocks)
+        assert m.bed(contigs) == 804
+        whole = [m.bed_text(c) for c in range(2)]
+        for c in range(2):
+            assert whole[c] == M.text(want[1][402 * c:402 * (c + 1)], names[c])
+            assert len(whole[c]) > 2 * 4096                   # more than one piece of 4096 bytes
+        long_lines = [l for l in whole[1].split(b"\n") if len(l) > 4096]
+        assert 0 < len(long_lines) < 10 and not [l for l in whole[0].split(b"\n") if len(l) > 4096]
+        for piece in (4096, None):
+            for c in range(2):
+                path = str(tmp_path / ("c%d.%s.bed" % (c, piece)))
+                if piece:
+                    os.environ["MMT_MERGED_TEXT_PIECE"] = str(piece)
+                try:
+                    m.write_bed(c, path)
+                finally:
+                    os.environ.pop("MMT_MERGED_TEXT_PIECE", None)
+                assert open(path, "rb").read() == whole[c], (piece, c)
+                assert not os.path.exists(path + ".tmp")
+
+
 def test_results_are_dropped_with_the_blocks_and_the_table(engine):
     import mumemto_amd
     t = collmodel.make_table(93, 300, 4, inversions=[(2, 40, 200)])

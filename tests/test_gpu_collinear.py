@@ -122,6 +122,16 @@ def test_tile_edges(engine, n):
     check(engine, t, 0, 300, n)
 
 
+def test_the_only_descent_of_a_column_lies_across_a_tile_of_the_extraction(engine):
+    """65 rows: row 64 is lane 0 of the second tile of the transpose and reads the key before it from the table; in column 2
+    it lies in front of every other row, the column's only descent, so the column must be sorted and the last pair is cut"""
+    lens, starts, strands = M.make_table(65, 65, 3, gaps=(0, 50), base=100000)
+    starts[64, 2] = 5
+    assert all(np.nonzero(np.diff(starts[:, c]) < 0)[0].tolist() == ([63] if c == 2 else []) for c in range(3))
+    _, want, stats = check(engine, (lens, starts, strands), 1000)
+    assert want.tolist() == [[0, 63]] and stats["cols_sorted"] == 1 and stats["cols_ascending"] == 2
+
+
 def test_one_block_covers_every_row_and_none_at_all(engine):
     t = M.make_table(11, 4097, 3, gaps=(0, 50))
     _, want, _ = check(engine, t, 1000)

@@ -114,6 +114,23 @@ def shaped_table():
     return M.block_table(cols, bases=[1 << 33, 0, 0, 1 << 34, 0, 5, 0, 0])
 
 
+@pytest.mark.parametrize("blocks", [65, 129])
+def test_the_only_descent_of_a_column_lies_across_a_tile_of_the_extraction(engine, blocks):
+    """the keys of the block heads leave the table 64 blocks a tile, and lane 0 of a tile reads the key before it from the
+    table, through the block list: in column 2 the blocks 64 .. lie in front of block 0, so that its keys descend between
+    blocks 63 and 64 and nowhere else (with 129 blocks the third tile begins on an ascent); the column must be sorted.
+    Column 1 carries a reversed segment, and with it the calls"""
+    rotated = np.concatenate([np.arange(64, blocks), np.arange(64)])
+    minus_segment = np.ones(blocks, bool)
+    minus_segment[10:21] = False
+    table, blk = M.block_table([(M.reversed_segments(blocks, [(10, 20)]), minus_segment), (rotated, np.ones(blocks, bool))])
+    heads = table[1][blk[:, 0].astype(np.int64), 2]
+    assert np.nonzero(np.diff(heads) < 0)[0].tolist() == [63]
+    want, stats = check(engine, table, blk, tag=blocks)
+    assert len(want) == 1 and want[0][0] == 1
+    assert stats["cols_sorted"] == 2 and stats["cols_ascending"] == 0 and stats["runs"] == 1
+
+
 @pytest.fixture(scope="module")
 def shaped(engine):
     table, blk = shaped_table()
