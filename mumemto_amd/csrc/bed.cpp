@@ -21,7 +21,7 @@ namespace {
 
 // room for `want` records in m.d_bed_records; the first `have` records stay
 void reserve_records(MergedRows& m, size_t have, size_t want, hipStream_t st) {
-    grow_keep(m.d_bed_records, have * bk::RECORD_FIELDS, want * bk::RECORD_FIELDS, st);
+    grow_keep(m.d_bed_records, want * bk::RECORD_FIELDS, have * bk::RECORD_FIELDS, grow_by_doubling, st);
 }
 
 // the number of set flags: the last flag and its number

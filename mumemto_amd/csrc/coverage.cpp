@@ -38,7 +38,7 @@ void coverage(Engine& e, MergedRows& m, const int64_t* seq_lengths, int64_t seq_
     m.has_coverage = false;
     std::vector<uint64_t> covered(nd, 0), run_begin((size_t)nd + 1, 0);
     size_t n_runs = 0;
-    grow_keep(m.d_runs, 0, 2, st);
+    grow_keep(m.d_runs, 2, 0, grow_by_doubling, st);
 
     if (n && first < last) {
         const uint32_t n_cols = last - first, tiles = cvk::scan_tiles(n);
@@ -96,7 +96,7 @@ void coverage(Engine& e, MergedRows& m, const int64_t* seq_lengths, int64_t seq_
                 run_begin[c0 + c] = n_runs;
                 const size_t col_runs = (size_t)(h_res[2] & 0xffffffffull);
                 if (col_runs) {
-                    grow_keep(m.d_runs, 2 * n_runs, 2 * (n_runs + col_runs), st);
+                    grow_keep(m.d_runs, 2 * (n_runs + col_runs), 2 * n_runs, grow_by_doubling, st);
                     laps.begin(3);
                     prims::exclusive_sum_u32(temp, heads.get(), numbered.get(), n, st);
                     cvk::write_runs(b, en, heads.get(), numbered.get(), n, r + 1, m.d_runs.get() + 2 * n_runs, st);

@@ -186,4 +186,15 @@ inline void d2h(std::vector<T>& dst, const T* src, size_t n, hipStream_t s) {
     MMT_HIP(hipStreamSynchronize(s));
 }
 
+// one 32-bit value, read back (synchronises the stream)
+inline uint32_t read_u32(const uint32_t* d, hipStream_t s) {
+    uint32_t v = 0;
+    MMT_HIP(hipMemcpyAsync(&v, d, 4, hipMemcpyDeviceToHost, s));
+    MMT_HIP(hipStreamSynchronize(s));
+    return v;
+}
+
+// the bits that hold v -- the bits a radix sort has to look at for keys whose OR is v --, at least one
+inline int bit_width_u64(uint64_t v) { int b = 0; while (v) { b++; v >>= 1; } return b ? b : 1; }
+
 }  // namespace mmt

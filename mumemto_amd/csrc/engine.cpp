@@ -8,12 +8,11 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "merged_tools.hpp"
 #include "prims.hpp"
 #include "rows_kernels.hpp"
 
 namespace mmt {
-
-static int bit_width_u64(uint64_t v) { int b = 0; while (v) { b++; v >>= 1; } return b; }
 
 // (64 MB: page-locking costs 0.19 s per GB when a block is made and 0.13 s per GB when the process ends -- four blocks of
 // 256 MB were a quarter of a second of the bench workload's 2.2 s from process start to exit)
@@ -369,9 +368,7 @@ void Engine::suffix_sort() {
     std::vector<uint64_t> hist;
     d2h(hist, d_hist_.get(), 256, stream_);
     uint8_t code[256];
-    int sigma = 0;
-    for (int c = 0; c < 256; c++) code[c] = hist[c] ? (uint8_t)(++sigma) : 0;
-    int bits = std::max(1, bit_width_u64((uint64_t)sigma));
+    int bits = bit_width_u64((uint64_t)symbol_codes(hist, 0, false, code));
     int chars = std::min(64 / bits, 64);
     d_code_.ensure(256);
     MMT_HIP(hipMemcpyAsync(d_code_.get(), code, 256, hipMemcpyHostToDevice, stream_));
@@ -439,19 +436,9 @@ void Engine::release_sort_scratch() {
     MMT_HIP(hipStreamSynchronize(stream_));
     sorter_.release();
     d_temp_.release();                               // (library scratch of the sorts: as large as their inputs)
-    std::unique_ptr<PfpState> fresh(new PfpState());
-    const PfpState& S = *pfp_;
-    fresh->w = S.w; fresh->p = S.p; fresh->n_cuts = S.n_cuts; fresh->n_phrases = S.n_phrases; fresh->n_distinct = S.n_distinct;
-    fresh->dict_len = S.dict_len; fresh->n_groups = S.n_groups; fresh->rounds_dict = S.rounds_dict; fresh->run_refined = S.run_refined;
-    fresh->rounds_parse = S.rounds_parse; fresh->n_entries = S.n_entries; fresh->n_fallback = S.n_fallback;
-    fresh->emit_launches = S.emit_launches;
-    fresh->bwt_ready = S.bwt_ready;
-    // (what the bucket-wise producer's share was: Engine::kmer_in_share answers after the run)
-    fresh->guided = S.guided; fresh->expand = S.expand; fresh->g_prefix = S.g_prefix; fresh->g_bits = S.g_bits;
-    fresh->g_share_lo = S.g_share_lo; fresh->g_share_hi = S.g_share_hi; fresh->g_share_valid = S.g_share_valid;
-    std::memcpy(fresh->g_code, S.g_code, sizeof(S.g_code));
-    std::memcpy(fresh->ms, S.ms, sizeof(S.ms));
-    pfp_ = std::move(fresh);
+    const PfpSummary summary = *pfp_;                // (pfp.hpp: the half of the state that outlives its tables)
+    pfp_.reset(new PfpState());
+    static_cast<PfpSummary&>(*pfp_) = summary;
 }
 
 void Engine::release_columns(bool keep_anchor_ranks) {
@@ -476,17 +463,6 @@ bool Engine::wants_lean() const {
 }
 
 // ---- A5 ------------------------------------------------------------------------
-// keeps the first `used` elements when the buffer has to grow
-template <typename T>
-static void grow_keep(DevBuf<T>& buf, size_t need, size_t used, hipStream_t s) {
-    if (need <= buf.size()) return;
-    DevBuf<T> bigger;
-    bigger.ensure(need + need / 4);
-    if (used) MMT_HIP(hipMemcpyAsync(bigger.get(), buf.get(), used * sizeof(T), hipMemcpyDeviceToDevice, s));
-    MMT_HIP(hipStreamSynchronize(s));
-    buf.swap(bigger);
-}
-
 // ---- the scan, window by window ---------------------------------------------------------------------------------
 // The stream is scanned in windows of suffix-array positions.  A window carries a left extension long enough for every
 // walk; candidates carry window-relative positions, accepted rows absolute ones.  The producers that emit the columns
@@ -595,7 +571,7 @@ bool Engine::scan_window(ScanState& S, const ColWindow& w, const mmt_params& p) 
     // verification + thresholds of this window's candidates
     EventPair& ev = next_range_event(S, 2);
     ev.start(st);
-    grow_keep(d_rows_, std::max<size_t>(S.rows_used + found, 1), S.rows_used, st);
+    grow_keep(d_rows_, std::max<size_t>(S.rows_used + found, 1), S.rows_used, grow_by_quarter, st);
     k::VerifyArgs v;
     v.cand = d_cand_.get(); v.n_cand = found; v.sa = w.sa; v.base = w.base; v.sa_off = w.sa_off; v.lcp = w.lcp;
     v.d_doc_start = d_doc_start_.get(); v.n_docs = (uint32_t)N;
@@ -618,9 +594,9 @@ bool Engine::scan_window(ScanState& S, const ColWindow& w, const mmt_params& p) 
         MMT_HIP(hipMemcpyAsync(&last[1], d_cap_cnt_.get() + (fresh - 1), 8, hipMemcpyDeviceToHost, st));
         MMT_HIP(hipStreamSynchronize(st));
         const uint64_t total = last[0] + last[1];
-        grow_keep(d_pool_lo_, (size_t)(pool_used_ + total + 16), (size_t)pool_used_, st);
-        if (wide_) grow_keep(d_pool_hi_, (size_t)(pool_used_ + total + 16), (size_t)pool_used_, st);
-        grow_keep(d_rows_pool_, std::max<size_t>(r, 1), S.rows_used, st);
+        grow_keep(d_pool_lo_, (size_t)(pool_used_ + total + 16), (size_t)pool_used_, grow_by_quarter, st);
+        if (wide_) grow_keep(d_pool_hi_, (size_t)(pool_used_ + total + 16), (size_t)pool_used_, grow_by_quarter, st);
+        grow_keep(d_rows_pool_, std::max<size_t>(r, 1), S.rows_used, grow_by_quarter, st);
         SaCol pool; pool.lo = d_pool_lo_.get(); pool.hi = wide_ ? d_pool_hi_.get() : nullptr;
         SaCol win = w.sa; win.lo += w.sa_off; if (win.hi) win.hi += w.sa_off;
         k::capture_rows(d_rows_.get() + S.rows_used, (uint32_t)fresh, d_cap_off_.get(), pool_used_, win, w.base, pool,

@@ -305,6 +305,18 @@ private:
     void guided_prepare();
     void guided_check_errors(const char* what);
     void build_giant(const std::vector<uint64_t>& hist);
+    // The steps the parse proper and the bucket-wise producer share (pfp.cpp).  Their callers own every buffer that outlives a
+    // step and release it, and the sorter, where they always did: the steps allocate in the callers' order and release nothing
+    // but their own locals.
+    static int symbol_codes(const std::vector<uint64_t>& hist, int lowest, bool dollar, uint8_t code[256]);
+    struct RunEnds { DevBuf<uint32_t> ends, sorted, count; };        // ends of the long runs of one symbol (RunRefine)
+    struct DictLcpScratch { DevBuf<uint32_t> plcp, counts, huge; };
+    int sort_dictionary(const uint8_t* dict, uint32_t nd, const std::vector<uint64_t>& hist, DevBuf<uint8_t>& code, uint32_t reserve,
+                        int chars_cap, DevBuf<uint32_t>& sa, DevBuf<uint32_t>& rank, RunEnds* run_list);
+    void dictionary_lcp(const uint8_t* dict, uint32_t nd, uint32_t* sa, const uint32_t* esuf, const uint8_t* ebw,
+                        DevBuf<uint32_t>& lcp, DictLcpScratch& X, uint32_t cap, const char* whose);
+    void sort_parse();
+    void build_inverted_lists(bool rec12, bool drop_other_form, uint32_t pos_bits, uint32_t* k_in, uint32_t* v_in);
     void pfp_stream(ScanState& S, const mmt_params& p);
     void pfp_emit_window(uint64_t b0, uint64_t c1, int set);
     uint64_t pfp_first_tile(uint64_t b0);         // emitter tile in which the group covering stream entry b0 + 1 begins

@@ -24,15 +24,6 @@
 
 namespace mmt {
 
-static int bit_width_u64(uint64_t v) { int b = 0; while (v) { b++; v >>= 1; } return b; }
-
-static uint32_t read_u32(const uint32_t* d, hipStream_t s) {
-    uint32_t v = 0;
-    MMT_HIP(hipMemcpyAsync(&v, d, 4, hipMemcpyDeviceToHost, s));
-    MMT_HIP(hipStreamSynchronize(s));
-    return v;
-}
-
 namespace {
 
 // scratch of one batch (capacity elements)
@@ -373,11 +364,9 @@ void Engine::guided_prepare() {
     std::vector<uint64_t> hist;
     d2h(hist, d_hist_.get(), 256, st);
     uint8_t code[256];
-    int sigma = 0;
-    for (int c = 0; c < 256; c++) code[c] = (hist[c] || c == 2) ? (uint8_t)(++sigma) : 0;
     gk::Ctx& ctx = S.gctx;
     ctx = gk::Ctx{};
-    ctx.bits = std::max(1, bit_width_u64((uint64_t)sigma));
+    ctx.bits = bit_width_u64((uint64_t)symbol_codes(hist, 0, true, code));
     ctx.chars = std::min(63 / ctx.bits, 63);
     // Bins of leading characters: every interval the scan can report (LCP value >= the minimum match length) lies inside
     // one bin as long as a bin's prefix is not longer than that length -- SURVEY.md 8(e) -- so that the pieces of the
@@ -446,25 +435,23 @@ void Engine::guided_prepare() {
     mark("phrase-end tables");
     // ---- the bins of the text suffixes (leading characters) ----
     S.g_nbins = 1u << (ctx.bits * prefix_chars);
-    {
+    auto bin_histogram = [&](std::vector<uint64_t>& bins) {      // of the suffixes ctx selects: all, or those ctx.repbits marks
+        const uint32_t slots = std::max<uint32_t>(S.g_nbins, 4096u);
         DevBuf<uint64_t> d_bins;
-        d_bins.ensure(std::max<uint32_t>(S.g_nbins, 4096u));
-        MMT_HIP(hipMemsetAsync(d_bins.get(), 0, (size_t)std::max<uint32_t>(S.g_nbins, 4096u) * 8, st));
+        d_bins.ensure(slots);
+        MMT_HIP(hipMemsetAsync(d_bins.get(), 0, (size_t)slots * 8, st));
         gk::bin_hist(ctx, prefix_chars, d_bins.get(), st);
-        d2h(S.g_bins, d_bins.get(), std::max<uint32_t>(S.g_nbins, 4096u), st);
-    }
+        d2h(bins, d_bins.get(), slots, st);
+    };
+    bin_histogram(S.g_bins);
     S.g_bins_rep.clear(); S.g_repbits.release();
     if (S.expand) {
         // expansion: which occurrence stands for its distinct phrase, and how many suffixes of each bin start in one
         S.g_repbits.ensure(((size_t)m + 31) / 32 + 2);
         gk::rep_bits(S.pid.get(), S.rep.get(), m, S.g_repbits.get(), st);
-        DevBuf<uint64_t> d_bins;
-        d_bins.ensure(std::max<uint32_t>(S.g_nbins, 4096u));
-        MMT_HIP(hipMemsetAsync(d_bins.get(), 0, (size_t)std::max<uint32_t>(S.g_nbins, 4096u) * 8, st));
         ctx.repbits = S.g_repbits.get();
-        gk::bin_hist(ctx, prefix_chars, d_bins.get(), st);
+        bin_histogram(S.g_bins_rep);
         ctx.repbits = nullptr;
-        d2h(S.g_bins_rep, d_bins.get(), std::max<uint32_t>(S.g_nbins, 4096u), st);
     }
     S.err.ensure(16);
     MMT_HIP(hipMemsetAsync(S.err.get(), 0, 64, st));
@@ -498,20 +485,12 @@ void Engine::guided_prepare() {
     // ---- suffix array of the parse (parse.hpp:85), LCP of adjacent parse suffixes (pfp.hpp:210-244) ----
     e5.start(st);
     t0 = now();
-    S.sa_p.ensure(m); S.isa_p.ensure(m);
-    {
-        const int pbits = std::max(1, bit_width_u64((uint64_t)D));
-        const int pchars = std::max(1, 64 / pbits);
-        sorter_.reserve(m);
-        pk::pack_keys_u32(S.parse.get(), m, pbits, pchars, sorter_.keys_in(), sorter_.vals_in(), st);
-        S.rounds_parse = sorter_.sort(m, pbits * pchars, (uint64_t)pchars, S.sa_p.get(), S.isa_p.get(), d_temp_, st);
-        MMT_HIP(hipStreamSynchronize(st));
-        sorter_.release();
-    }
+    sort_parse();
+    MMT_HIP(hipStreamSynchronize(st));
+    sorter_.release();
     S.plcp.build(text_ref(), n + 1 + w, S.sa_p.get(), S.pid.get(), S.pstart.get(), W, m, d_temp_, st);
     if (S.expand) {
-        // the inverted lists of the distinct phrases (parse.hpp:106-134), as for the emitter of the parse proper
-        // (pfp.cpp::pfp_prepare_emitter): occurrences ordered by (phrase, rank of the following parse suffix)
+        // the inverted lists of the distinct phrases, as for the emitter of the parse proper (pfp.cpp::build_inverted_lists)
         const int shift = bit_width_u64((uint64_t)m + 1);
         const uint32_t pos_bits = W ? (uint32_t)bit_width_u64(n + w + 1) : 32u;
         const bool rec12 = (uint32_t)shift + pos_bits > 64 || sw::on(sw::MMT_OCC_REC12);
@@ -520,21 +499,7 @@ void Engine::guided_prepare() {
         {
             DevBuf<uint32_t> k_in, v_in;
             k_in.ensure((size_t)m + 1); v_in.ensure((size_t)m + 1);
-            pk::occ_sequence(S.sa_p.get(), S.pid.get(), m, D, k_in.get(), v_in.get(), st);
-            prims::sort_pairs_u32_u32(d_temp_, k_in.get(), S.occ_ids.get(), v_in.get(), S.occ_ts.get(), (size_t)m + 1, 0,
-                                      std::max(1, bit_width_u64((uint64_t)D)), st);
-            if (rec12) {
-                S.occ.release(); S.occ_sl.release();
-                S.occ12.ensure(3 * (size_t)m + 4);
-                pk::occ_finish12(S.occ_ids.get(), S.occ_ts.get(), S.sa_p.get(), S.pstart.get(), W, m, S.occ_start.get(),
-                                 S.occ12.get(), S.plcp.sl.get(), st);
-            } else {
-                S.occ12.release();
-                S.occ.ensure(m); S.occ_sl.ensure(m);
-                pk::occ_finish(S.occ_ids.get(), S.occ_ts.get(), S.sa_p.get(), S.pstart.get(), m, S.occ_start.get(), S.occ.get(),
-                               pos_bits, S.plcp.sl.get(), S.occ_sl.get(), W, st);
-            }
-            MMT_HIP(hipStreamSynchronize(st));
+            build_inverted_lists(rec12, true, pos_bits, k_in.get(), v_in.get());
         }
         S.occ_ids.release(); S.occ_ts.release();
         S.ptab.ensure((size_t)D * 16 + 16);
@@ -567,8 +532,9 @@ void Engine::guided_prepare() {
 
 // Giant phrases -- longer than 24 first-key lengths (504 bases): a run of N, a microsatellite, any stretch without a
 // trigger of the parse (newscan.hpp:265-325) -- would be refined 21 characters per round by every suffix that starts in
-// them.  Their suffixes are sorted ONCE instead, as a dictionary of their own with the machinery of the parse proper (unique
-// terminators, prefix doubling: a megabase of N is 20 rounds), with its LCP array (irreducible entries + PLCP chain) and a
+// them.  Their suffixes are sorted ONCE instead, as a dictionary of their own with the steps of the parse proper
+// (sort_dictionary, dictionary_lcp in pfp.cpp: unique terminators, prefix doubling: a megabase of N is 20 rounds), with its
+// LCP array (irreducible entries + PLCP chain) and a
 // range-minimum structure on it; a comparison that is undecided 504 characters into alpha continues on those ranks
 // (gk::cmp_rest, k_round_keys), and the LCP of two such suffixes is a range minimum.
 void Engine::build_giant(const std::vector<uint64_t>& hist) {
@@ -650,54 +616,23 @@ void Engine::build_giant(const std::vector<uint64_t>& hist) {
     prims::exclusive_sum_u32(d_temp_, glen.get(), gstart.get(), nG, st);
     MMT_HIP(hipMemsetAsync(dmap.get(), 0xff, (size_t)D * 4, st));
     gk::giant_map(gids.get(), gstart.get(), nG, dmap.get(), st);
-    // the giant dictionary, its suffix array (unique terminators: prefix doubling as for the parse proper's dictionary)
+    // the giant dictionary, its suffix array (unique terminators: prefix doubling as for the parse proper's dictionary; its own
+    // code buffer: d_code_ holds the codes of the batches by now)
     DevBuf<uint8_t> dict, code_d, ebw;
     DevBuf<uint64_t> dinfo;
     dict.ensure((size_t)nd + 64); dinfo.ensure(nd);
     MMT_HIP(hipMemsetAsync(dict.get() + nd, 0, 64, st));
     pk::copy_dict(text_ref(), S.pstart.get(), S.plen.get(), which.get(), gstart.get(), nG, dict.get(), dinfo.get(), nd, false, W, st);
-    uint8_t code[256];
-    int sigma = 0;
-    // (0x00 -- once, the last byte of the dictionary -- and the phrase terminator 0x01 share code 0 with the padding behind
-    // the end: nothing is compared behind a terminator, terminators are ordered by position.  Dollar, the document
-    // separator, A C G T and N then fit three bits: 21 characters per 64-bit key instead of 15)
-    for (int c = 0; c < 256; c++) code[c] = (c > 1 && (hist[c] || c == 2)) ? (uint8_t)(++sigma) : 0;
-    const int bits = std::max(1, bit_width_u64((uint64_t)sigma)), chars = std::min(63 / bits, 63);
-    code_d.ensure(256);
-    MMT_HIP(hipMemcpyAsync(code_d.get(), code, 256, hipMemcpyHostToDevice, st));
-    DevBuf<uint32_t> sa_g, esuf, ephr, plcp, cnt2, huge;
-    sa_g.ensure(nd); S.gi_isa.ensure(nd);
-    sorter_.reserve(nd);
-    k::pack_keys(dict.get(), nd, code_d.get(), bits, chars, (uint32_t)code[1], sorter_.keys_in(), sorter_.vals_in(), st);
-    const int rounds = sorter_.sort(nd, bits * chars + 1, (uint64_t)chars, sa_g.get(), S.gi_isa.get(), d_temp_, st, true);
+    DevBuf<uint32_t> sa_g, esuf, ephr;
+    DictLcpScratch lcp_scratch;
+    const int rounds = sort_dictionary(dict.get(), nd, hist, code_d, nd, 63, sa_g, S.gi_isa, nullptr);
     MMT_HIP(hipStreamSynchronize(st));
     sorter_.release();
     esuf.ensure(nd); ephr.ensure(nd); ebw.ensure(nd);
     pk::entry_info(sa_g.get(), dinfo.get(), dict.get(), nd, false, esuf.get(), ephr.get(), ebw.get(), st);
-    // its LCP array (irreducible entries compared directly, the rest by the PLCP chain), groups of equal strings
-    plcp.ensure((size_t)nd + 16); cnt2.ensure(4); S.gi_lcp.ensure(((size_t)nd + 3) / 4 * 4 + 16);
-    {
-        DevBuf<uint8_t> longs;
-        uint32_t cap = std::max<uint32_t>(nd / 64 + 4096, 1u << 16), found = 0;
-        for (int attempt = 0;; attempt++) {
-            longs.ensure((size_t)cap * sizeof(k::LongLcpLim));
-            pk::dict_irreducible(dict.get(), nd, sa_g.get(), esuf.get(), ebw.get(), plcp.get(), longs.get(), cnt2.get(), cap, st);
-            found = read_u32(cnt2.get(), st);
-            if (found <= cap) break;
-            if (attempt) throw std::runtime_error("long-match list overflow in the giant dictionary's LCP construction");
-            cap = found + 1024;
-        }
-        if (found) {
-            huge.ensure((size_t)found + 1);
-            k::long_lcp_lim(dict.get(), nd, longs.get(), found, plcp.get(), huge.get(), cnt2.get() + 1, st);
-        }
-        d_temp_.ensure(k::plcp_running_max_scratch(nd));
-        k::plcp_running_max(plcp.get(), nd, d_temp_.get(), st);
-        SaCol sd; sd.lo = sa_g.get(); sd.hi = nullptr;
-        k::lcp_gather(plcp.get(), sd, 0, nd, S.gi_lcp.get(), st);
-        pk::dict_lcp_clamp(S.gi_lcp.get(), esuf.get(), nd, st);
-        MMT_HIP(hipStreamSynchronize(st));
-    }
+    // its LCP array, groups of equal strings
+    dictionary_lcp(dict.get(), nd, sa_g.get(), esuf.get(), ebw.get(), S.gi_lcp, lcp_scratch,
+                   std::max<uint32_t>(nd / 64 + 4096, 1u << 16), "giant dictionary");
     S.gi_grp.ensure(nd);
     gk::giant_group_flags(esuf.get(), S.gi_lcp.get(), nd, S.gi_grp.get(), st);
     prims::inclusive_sum_u32(d_temp_, S.gi_grp.get(), S.gi_grp.get(), nd, st);

@@ -63,7 +63,7 @@ void inversion_calls(Engine& e, MergedRows& m, int64_t max_length, InversionStat
     m.has_calls = false; m.n_calls = 0;
     const uint32_t B = (uint32_t)m.n_blocks, nd = (uint32_t)m.n_docs;
     S.blocks = B;
-    grow_keep(m.d_calls, 0, ik::CALL_FIELDS, st);
+    grow_keep(m.d_calls, ik::CALL_FIELDS, 0, grow_by_doubling, st);
 
     // a run is at least two blocks, and column 0 orders the blocks themselves
     if (B >= 2 && nd >= 2) {
@@ -118,7 +118,7 @@ void inversion_calls(Engine& e, MergedRows& m, int64_t max_length, InversionStat
                     MMT_HIP(hipMemcpyAsync(&kept, count.get() + 2, 4, hipMemcpyDeviceToHost, st));
                     MMT_HIP(hipStreamSynchronize(st));
                     if (kept) {
-                        grow_keep(m.d_calls, m.n_calls * ik::CALL_FIELDS, (m.n_calls + kept) * ik::CALL_FIELDS, st);
+                        grow_keep(m.d_calls, (m.n_calls + kept) * ik::CALL_FIELDS, m.n_calls * ik::CALL_FIELDS, grow_by_doubling, st);
                         ik::compact(rec.get(), sel.get(), kept, m.d_calls.get() + m.n_calls * ik::CALL_FIELDS, st);
                         m.n_calls += kept;
                     }

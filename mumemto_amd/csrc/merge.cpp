@@ -23,8 +23,6 @@
 namespace mmt {
 namespace {
 
-int bit_width_u64(uint64_t v) { int b = 0; while (v) { b++; v >>= 1; } return b ? b : 1; }
-
 // One side of a fold step in anchor order (see merge_kernels.hpp).
 struct SideBuf {
     DevBuf<uint64_t> start;

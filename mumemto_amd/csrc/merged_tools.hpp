@@ -1,5 +1,5 @@
 // merged_tools.hpp -- host idioms the tools over a merged table share (collinear.cpp, inversion.cpp, coverage.cpp, bed.cpp):
-// the bit range of a sort, a record list that grows, the column batch plan, the per-column flags of a batch.
+// a record list that grows (the engine's row lists grow by it too), the column batch plan, the per-column flags of a batch.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -11,15 +11,17 @@
 
 namespace mmt {
 
-// the bits a radix sort has to look at for keys whose OR is v (at least one)
-inline int bit_width_u64(uint64_t v) { int b = 0; while (v) { b++; v >>= 1; } return b ? b : 1; }
-
-// room for `want` entries in a record list that is appended to; the first `have` entries stay
-inline void grow_keep(DevBuf<int64_t>& list, size_t have, size_t want, hipStream_t st) {
-    if (want <= list.size()) return;
-    DevBuf<int64_t> bigger;
-    bigger.ensure(std::max(want, 2 * list.size()));
-    if (have) MMT_HIP(hipMemcpyAsync(bigger.get(), list.get(), have * 8, hipMemcpyDeviceToDevice, st));
+// Room for `need` entries in a list that is appended to; the first `used` entries stay.  A list that has to grow gets
+// rule(need, its size now) entries: buffer sizes decide the heap's peak, so the engine's row lists and the tools' record
+// lists each keep the rule they were sized with.
+inline size_t grow_by_quarter(size_t need, size_t) { return need + need / 4; }               // the engine (engine.cpp)
+inline size_t grow_by_doubling(size_t need, size_t size) { return std::max(need, 2 * size); }   // the tools
+template <typename T>
+inline void grow_keep(DevBuf<T>& list, size_t need, size_t used, size_t (*rule)(size_t, size_t), hipStream_t st) {
+    if (need <= list.size()) return;
+    DevBuf<T> bigger;
+    bigger.ensure(rule(need, list.size()));
+    if (used) MMT_HIP(hipMemcpyAsync(bigger.get(), list.get(), used * sizeof(T), hipMemcpyDeviceToDevice, st));
     MMT_HIP(hipStreamSynchronize(st));
     list.swap(bigger);
 }

@@ -17,19 +17,134 @@
 
 namespace mmt {
 
-static int bit_width_u64(uint64_t v) { int b = 0; while (v) { b++; v >>= 1; } return b; }
-
-static uint32_t read_u32(const uint32_t* d, hipStream_t s) {
-    uint32_t v = 0;
-    MMT_HIP(hipMemcpyAsync(&v, d, 4, hipMemcpyDeviceToHost, s));
-    MMT_HIP(hipStreamSynchronize(s));
-    return v;
-}
-
 // exclusive prefix sum of 32-bit counts into a table of stream offsets
 static void offsets_from_counts(DevBuf<uint8_t>& temp, const uint32_t* counts, PosBuf& out, size_t n, hipStream_t s) {
     if (out.wide()) prims::exclusive_sum_u32_to_u64(temp, counts, out.p64(), n, s);
     else prims::exclusive_sum_u32(temp, counts, out.p32(), n, s);
+}
+
+// ---- steps the parse proper and the bucket-wise producer (guided.cpp) share ----------------------------------------------
+
+// Symbol codes from the byte histogram: 1 .. sigma, ascending with the byte value, for the bytes from `lowest` on that occur
+// -- and for Dollar (0x02) whether it occurs or not, if `dollar` --, 0 for every other byte.  Returns sigma.
+int Engine::symbol_codes(const std::vector<uint64_t>& hist, int lowest, bool dollar, uint8_t code[256]) {
+    int sigma = 0;
+    for (int c = 0; c < 256; c++) code[c] = (c >= lowest && (hist[c] || (dollar && c == 2))) ? (uint8_t)(++sigma) : 0;
+    return sigma;
+}
+
+// Suffix array `sa` and its inverse `rank` of a dictionary of terminated phrases: nd bytes, 0x01 behind every phrase, 0x00 at the
+// end, 64 zero bytes behind that.  `code`: the device copy of the code table; `reserve`: what the sorter is reserved for;
+// chars_cap: at most so many characters per key.  run_list (optional): room for the ends of the long runs of one symbol.
+// Returns the sorter's rounds; the sorter stays reserved.
+int Engine::sort_dictionary(const uint8_t* dict, uint32_t nd, const std::vector<uint64_t>& hist, DevBuf<uint8_t>& code_buf,
+                            uint32_t reserve, int chars_cap, DevBuf<uint32_t>& sa, DevBuf<uint32_t>& rank, RunEnds* run_list) {
+    hipStream_t st = stream_;
+    uint8_t code[256];
+    // (0x00 -- once, the last byte of the dictionary -- and the phrase terminator 0x01 share code 0 with the padding behind
+    // the end: nothing is compared behind a terminator, terminators are ordered by position.  Dollar, the document
+    // separator, A C G T and N then fit three bits: 21 characters per 64-bit key instead of 15)
+    const int sigma = symbol_codes(hist, 2, true, code);
+    const int bits = bit_width_u64((uint64_t)sigma);
+    // every 0x01 (end of a phrase) is a unique terminator, ordered by position: what follows it never matters, so
+    // a suffix is final as soon as the compared prefix reaches the end of its phrase (one key bit says so)
+    const int chars = std::min(std::min(63 / bits, 63), chars_cap);
+    code_buf.ensure(256);
+    MMT_HIP(hipMemcpyAsync(code_buf.get(), code, 256, hipMemcpyHostToDevice, st));
+    sa.ensure(nd); rank.ensure(nd);
+    sorter_.reserve(reserve);
+    // long runs of one symbol (assembly gaps, homopolymers): their ends are listed while the keys are packed, and the sorter
+    // orders the suffixes inside them by (end of the run, what follows) instead of doubling its way through (sorter.hpp)
+    const uint32_t run_cap = 1u << 20;
+    const bool want_runs = run_list && bits <= 3;
+    if (want_runs) {
+        run_list->ends.ensure(run_cap); run_list->count.ensure(4);
+        MMT_HIP(hipMemsetAsync(run_list->count.get(), 0, 16, st));
+    }
+    k::pack_keys(dict, nd, code_buf.get(), bits, chars, (uint32_t)code[1], sorter_.keys_in(), sorter_.vals_in(), st,
+                 want_runs ? run_list->ends.get() : nullptr, want_runs ? run_list->count.get() : nullptr, run_cap);
+    RunRefine runs;
+    if (want_runs) {
+        const uint32_t found = read_u32(run_list->count.get(), st);
+        if (found && found <= run_cap) {                     // (more than the list holds: plain doubling)
+            DevBuf<uint32_t>& run_sorted = run_list->sorted;
+            run_sorted.ensure((size_t)found * 3);            // sorted ends | two columns of dummy values
+            MMT_HIP(hipMemsetAsync(run_sorted.get() + found, 0, (size_t)found * 4, st));
+            prims::sort_pairs_u32_u32(d_temp_, run_list->ends.get(), run_sorted.get(), run_sorted.get() + found,
+                                      run_sorted.get() + 2 * (size_t)found, found, 0, 32, st);
+            runs.text = dict; runs.n = nd; runs.code = code_buf.get(); runs.bits = bits; runs.chars = chars; runs.sigma = sigma;
+            runs.ends = run_sorted.get(); runs.n_ends = found;
+        }
+    }
+    return sorter_.sort(nd, bits * chars + 1, (uint64_t)chars, sa.get(), rank.get(), d_temp_, st, true, runs.n_ends ? &runs : nullptr);
+}
+
+// LCP array of such a dictionary in suffix-array order (dictionary.hpp:133 takes it from gsacak): irreducible entries compared
+// directly, the others by the PLCP chain along the dictionary, then gathered into suffix-array order and clamped to the phrase
+// suffixes.  cap: the first capacity of the long-match list; `whose`: the dictionary's name in the overflow message.
+void Engine::dictionary_lcp(const uint8_t* dict, uint32_t nd, uint32_t* sa, const uint32_t* esuf, const uint8_t* ebw,
+                            DevBuf<uint32_t>& lcp, DictLcpScratch& X, uint32_t cap, const char* whose) {
+    hipStream_t st = stream_;
+    DevBuf<uint8_t> longs;
+    X.plcp.ensure((size_t)nd + 16); X.counts.ensure(4); lcp.ensure(((size_t)nd + 3) / 4 * 4 + 16);
+    uint32_t found = 0;
+    for (int attempt = 0;; attempt++) {
+        longs.ensure((size_t)cap * sizeof(k::LongLcpLim));
+        pk::dict_irreducible(dict, nd, sa, esuf, ebw, X.plcp.get(), longs.get(), X.counts.get(), cap, st);
+        found = read_u32(X.counts.get(), st);
+        if (found <= cap) break;
+        if (attempt) throw std::runtime_error(std::string("long-match list overflow in the ") + whose + "'s LCP construction");
+        cap = found + 1024;                              // rare: once more with the exact size
+    }
+    if (found) {
+        X.huge.ensure((size_t)found + 1);
+        k::long_lcp_lim(dict, nd, longs.get(), found, X.plcp.get(), X.huge.get(), X.counts.get() + 1, st);
+    }
+    d_temp_.ensure(k::plcp_running_max_scratch(nd));
+    k::plcp_running_max(X.plcp.get(), nd, d_temp_.get(), st);
+    SaCol sd; sd.lo = sa; sd.hi = nullptr;
+    k::lcp_gather(X.plcp.get(), sd, 0, nd, lcp.get(), st);
+    pk::dict_lcp_clamp(lcp.get(), esuf, nd, st);
+    MMT_HIP(hipStreamSynchronize(st));
+}
+
+// Suffix array S.sa_p of the parse and its inverse S.isa_p (parse.hpp:85): the ranks packed 64 / bits to a key; the sorter stays
+// reserved.
+void Engine::sort_parse() {
+    PfpState& S = *pfp_;
+    hipStream_t st = stream_;
+    const uint32_t m = S.n_phrases;
+    S.sa_p.ensure(m); S.isa_p.ensure(m);
+    const int pbits = bit_width_u64((uint64_t)S.n_distinct);
+    const int pchars = std::max(1, 64 / pbits);
+    sorter_.reserve(m);
+    pk::pack_keys_u32(S.parse.get(), m, pbits, pchars, sorter_.keys_in(), sorter_.vals_in(), st);
+    S.rounds_parse = sorter_.sort(m, pbits * pchars, (uint64_t)pchars, S.sa_p.get(), S.isa_p.get(), d_temp_, st);
+}
+
+// Inverted lists of the distinct phrases (parse.hpp:106-134): the parse positions ordered by (phrase, rank of the following parse
+// suffix), as 64-bit records S.occ with S.occ_sl, or -- rec12 -- as 12-byte records S.occ12.  drop_other_form: what an earlier run
+// left of the other form is released before this one is made (the bucket-wise producer; the parse proper lets it go behind its
+// lists).  The caller has S.occ_start, S.occ_ids and S.occ_ts in place and lends k_in / v_in, m + 1 entries each.
+void Engine::build_inverted_lists(bool rec12, bool drop_other_form, uint32_t pos_bits, uint32_t* k_in, uint32_t* v_in) {
+    PfpState& S = *pfp_;
+    const bool W = wide_;
+    hipStream_t st = stream_;
+    const uint32_t m = S.n_phrases, D = S.n_distinct;
+    pk::occ_sequence(S.sa_p.get(), S.pid.get(), m, D, k_in, v_in, st);
+    prims::sort_pairs_u32_u32(d_temp_, k_in, S.occ_ids.get(), v_in, S.occ_ts.get(), (size_t)m + 1, 0, bit_width_u64((uint64_t)D), st);
+    if (rec12) {
+        if (drop_other_form) { S.occ.release(); S.occ_sl.release(); }
+        S.occ12.ensure(3 * (size_t)m + 4);
+        pk::occ_finish12(S.occ_ids.get(), S.occ_ts.get(), S.sa_p.get(), S.pstart.get(), W, m, S.occ_start.get(),
+                         S.occ12.get(), S.plcp.sl.get(), st);
+    } else {
+        if (drop_other_form) S.occ12.release();
+        S.occ.ensure(m); S.occ_sl.ensure(m);
+        pk::occ_finish(S.occ_ids.get(), S.occ_ts.get(), S.sa_p.get(), S.pstart.get(), m, S.occ_start.get(), S.occ.get(),
+                       pos_bits, S.plcp.sl.get(), S.occ_sl.get(), W, st);
+    }
+    MMT_HIP(hipStreamSynchronize(st));
 }
 
 // A2 + the dictionary half of A3: phrases, distinct phrases, dictionary text with its suffix
@@ -194,46 +309,11 @@ void Engine::pfp_parse(uint32_t w, uint32_t p, bool keep_dict_inputs) {
 
     // -- suffix array of the dictionary (dictionary.hpp:133) ...
     e3.start(st);
-    uint8_t code[256];
-    int sigma = 0;
-    // (0x00 -- once, the last byte of the dictionary -- and the phrase terminator 0x01 share code 0 with the padding behind
-    // the end: nothing is compared behind a terminator, terminators are ordered by position.  Dollar, the document
-    // separator, A C G T and N then fit three bits: 21 characters per 64-bit key instead of 15)
-    for (int c = 0; c < 256; c++) code[c] = (c > 1 && (hist[c] || c == 2)) ? (uint8_t)(++sigma) : 0;
-    const int bits = std::max(1, bit_width_u64((uint64_t)sigma));
-    // every 0x01 (end of a phrase) is a unique terminator, ordered by position: what follows it never matters, so
-    // a suffix is final as soon as the compared prefix reaches the end of its phrase (one key bit says so)
-    int chars = std::min(63 / bits, 63);
-    if (sw::is_set(sw::MMT_DICT_KEY_CHARS)) chars = std::max(4, std::min(chars, sw::num(sw::MMT_DICT_KEY_CHARS, 0)));      // (tuning aid)
-    d_code_.ensure(256);
-    MMT_HIP(hipMemcpyAsync(d_code_.get(), code, 256, hipMemcpyHostToDevice, st));
-    S.sa_d.ensure(nd); S.rank_d.ensure(nd);
-    sorter_.reserve(slim ? nd : std::max(nd, m));
-    // long runs of one symbol (assembly gaps, homopolymers): their ends are listed while the keys are packed, and the sorter
-    // orders the suffixes inside them by (end of the run, what follows) instead of doubling its way through (sorter.hpp)
-    const uint32_t run_cap = 1u << 20;
-    DevBuf<uint32_t> run_ends, run_sorted, run_count;
-    const bool want_runs = bits <= 3 && !sw::on(sw::MMT_NO_RUN_REFINE);          // (MMT_NO_RUN_REFINE: plain doubling, A/B)
-    if (want_runs) {
-        run_ends.ensure(run_cap); run_count.ensure(4);
-        MMT_HIP(hipMemsetAsync(run_count.get(), 0, 16, st));
-    }
-    k::pack_keys(S.dict.get(), nd, d_code_.get(), bits, chars, (uint32_t)code[1], sorter_.keys_in(), sorter_.vals_in(), st,
-                 want_runs ? run_ends.get() : nullptr, want_runs ? run_count.get() : nullptr, run_cap);
-    RunRefine runs;
-    if (want_runs) {
-        const uint32_t found = read_u32(run_count.get(), st);
-        if (found && found <= run_cap) {                     // (more than the list holds: plain doubling)
-            run_sorted.ensure((size_t)found * 3);            // sorted ends | two columns of dummy values
-            MMT_HIP(hipMemsetAsync(run_sorted.get() + found, 0, (size_t)found * 4, st));
-            prims::sort_pairs_u32_u32(d_temp_, run_ends.get(), run_sorted.get(), run_sorted.get() + found,
-                                      run_sorted.get() + 2 * (size_t)found, found, 0, 32, st);
-            runs.text = S.dict.get(); runs.n = nd; runs.code = d_code_.get(); runs.bits = bits; runs.chars = chars; runs.sigma = sigma;
-            runs.ends = run_sorted.get(); runs.n_ends = found;
-        }
-    }
-    S.rounds_dict = sorter_.sort(nd, bits * chars + 1, (uint64_t)chars, S.sa_d.get(), S.rank_d.get(), d_temp_, st, true,
-                                 runs.n_ends ? &runs : nullptr);
+    // (MMT_DICT_KEY_CHARS: tuning aid, at least 4; a code has at most eight bits, so the 63 / bits characters of a key are 7 or more)
+    const int chars_cap = sw::is_set(sw::MMT_DICT_KEY_CHARS) ? std::max(4, sw::num(sw::MMT_DICT_KEY_CHARS, 0)) : 63;
+    RunEnds run_list;
+    S.rounds_dict = sort_dictionary(S.dict.get(), nd, hist, d_code_, slim ? nd : std::max(nd, m), chars_cap, S.sa_d, S.rank_d,
+                                    sw::on(sw::MMT_NO_RUN_REFINE) ? nullptr : &run_list);      // (MMT_NO_RUN_REFINE: plain doubling, A/B)
     S.run_refined = sorter_.run_refined();
     // (the sorter's 49 bytes per dictionary character were the idle half of the run's peak while the tables of the dictionary
     // were built: a fresh process maps, and gives back at its end, every byte of that peak)
@@ -247,32 +327,10 @@ void Engine::pfp_parse(uint32_t w, uint32_t p, bool keep_dict_inputs) {
     if (slim) S.dinfo.release();
     S.gflag.ensure(nd); S.pflag.ensure(nd); S.vflag.ensure(nd); S.gscan.ensure(nd); S.pscan.ensure(nd);
     S.prank.ensure(D); S.parse.ensure(m);
-    // LCP array of the dictionary (dictionary.hpp:133 takes it from gsacak): irreducible entries compared directly, the
-    // others by the PLCP chain along the dictionary, then gathered into suffix-array order
     {
-        DevBuf<uint32_t> plcp_d, counts, huge;
-        DevBuf<uint8_t> longs;
-        plcp_d.ensure((size_t)nd + 16); counts.ensure(4); S.lcp_d.ensure(((size_t)nd + 3) / 4 * 4 + 16);
-        uint32_t cap = std::max<uint32_t>(nd / 256 + 4096, 1u << 16), found = 0;
-        for (int attempt = 0;; attempt++) {
-            longs.ensure((size_t)cap * sizeof(k::LongLcpLim));
-            pk::dict_irreducible(S.dict.get(), nd, S.sa_d.get(), S.esuf.get(), S.ebw.get(), plcp_d.get(), longs.get(),
-                                 counts.get(), cap, st);
-            found = read_u32(counts.get(), st);
-            if (found <= cap) break;
-            if (attempt) throw std::runtime_error("long-match list overflow in the dictionary's LCP construction");
-            cap = found + 1024;                              // rare: once more with the exact size
-        }
-        if (found) {
-            huge.ensure((size_t)found + 1);
-            k::long_lcp_lim(S.dict.get(), nd, longs.get(), found, plcp_d.get(), huge.get(), counts.get() + 1, st);
-        }
-        d_temp_.ensure(k::plcp_running_max_scratch(nd));
-        k::plcp_running_max(plcp_d.get(), nd, d_temp_.get(), st);
-        SaCol sd; sd.lo = S.sa_d.get(); sd.hi = nullptr;
-        k::lcp_gather(plcp_d.get(), sd, 0, nd, S.lcp_d.get(), st);
-        pk::dict_lcp_clamp(S.lcp_d.get(), S.esuf.get(), nd, st);
-        MMT_HIP(hipStreamSynchronize(st));
+        DictLcpScratch scratch;
+        dictionary_lcp(S.dict.get(), nd, S.sa_d.get(), S.esuf.get(), S.ebw.get(), S.lcp_d, scratch,
+                       std::max<uint32_t>(nd / 256 + 4096, 1u << 16), "dictionary");
     }
     S.segmin.ensure(nd);
     pk::group_flags(S.esuf.get(), S.lcp_d.get(), nd, w, S.gflag.get(), S.pflag.get(), S.vflag.get(), S.segmin.get(), st);
@@ -315,12 +373,7 @@ void Engine::pfp_prepare_emitter(uint32_t w) {
     const uint32_t m = S.n_phrases, D = S.n_distinct;
     EventPair e5, e6;
     e5.start(st);
-    S.sa_p.ensure(m); S.isa_p.ensure(m);
-    const int pbits = std::max(1, bit_width_u64((uint64_t)D));
-    const int pchars = std::max(1, 64 / pbits);
-    sorter_.reserve(m);
-    pk::pack_keys_u32(S.parse.get(), m, pbits, pchars, sorter_.keys_in(), sorter_.vals_in(), st);
-    S.rounds_parse = sorter_.sort(m, pbits * pchars, (uint64_t)pchars, S.sa_p.get(), S.isa_p.get(), d_temp_, st);
+    sort_parse();
     if (slim) { MMT_HIP(hipStreamSynchronize(st)); sorter_.release(); S.isa_p.release(); S.parse.release(); }
     // LCP of adjacent parse suffixes + range minima: every LCP value of the stream follows from them locally
     S.plcp.build(text_ref(), n + 1 + w, S.sa_p.get(), S.pid.get(), S.pstart.get(), W, m, d_temp_, st);
@@ -344,13 +397,7 @@ void Engine::pfp_prepare_emitter(uint32_t w) {
             sorter_.u32_a().ensure((size_t)m + 1); sorter_.u32_b().ensure((size_t)m + 1);     // scratch
             k_in = sorter_.u32_a().get(); v_in = sorter_.u32_b().get();
         }
-        pk::occ_sequence(S.sa_p.get(), S.pid.get(), m, D, k_in, v_in, st);
-        prims::sort_pairs_u32_u32(d_temp_, k_in, S.occ_ids.get(), v_in, S.occ_ts.get(), (size_t)m + 1, 0,
-                                  std::max(1, bit_width_u64((uint64_t)D)), st);
-        S.occ_sl.ensure(m);
-        pk::occ_finish(S.occ_ids.get(), S.occ_ts.get(), S.sa_p.get(), S.pstart.get(), m, S.occ_start.get(),
-                       S.occ.get(), pos_bits, S.plcp.sl.get(), S.occ_sl.get(), W, st);
-        MMT_HIP(hipStreamSynchronize(st));
+        build_inverted_lists(false, false, pos_bits, k_in, v_in);       // (never the 12-byte records: see the check above)
     }
     if (slim) { S.occ_ids.release(); S.occ_ts.release(); S.sa_p.release(); S.pid.release(); S.pstart.release(); }
     // valid dictionary suffixes in dictionary suffix-array order, compacted ("entries")

@@ -11,15 +11,32 @@
 
 namespace mmt {
 
-struct PfpState {
+// The state has two lifetimes.  PfpSummary is what a run reports after it (mmt_pfp_counts, mmt_pfp_stage_ms, mmt_kmer_in_share):
+// plain values, copied as a whole when a slim run -- MUMEMTO_LEAN, wide texts, one-shot runs -- gives its tables back
+// (Engine::release_sort_scratch).  PfpState adds the device buffers and the per-run tables that go with them.  A new field
+// belongs in the summary when something asks for it after the run and it is a plain value; everything that owns memory, points
+// into a buffer or only means something while the tables exist belongs in PfpState, which starts from its defaults again.
+struct PfpSummary {
     uint32_t w = 0, p = 0;
     uint32_t n_cuts = 0, n_phrases = 0, n_distinct = 0, dict_len = 0, n_groups = 0;
-    bool have_parse = false;
     bool guided = false;    // the dictionary stage was skipped: Engine::suffix_sort_guided sorts the text suffixes themselves
     bool expand = false;    // ... one representative per (distinct phrase, offset) only, expanded by the emitter (guided.cpp)
     int rounds_dict = 0, rounds_parse = 0;
     uint64_t run_refined = 0;         // dictionary suffixes ordered by their long run of one symbol (sorter.hpp, RunRefine)
     float ms[8] = {0};   // parse, dedup, dict build, dict SA, dict LCP + groups, parse SA, inverted lists + emitter, total
+    uint32_t n_entries = 0, n_fallback = 0, emit_launches = 0;
+    bool bwt_ready = false;
+    // what the bucket-wise producer's share was (Engine::kmer_in_share answers after the run): the bins the last stream of this
+    // producer took (a rank's share: Engine::set_scan_shard), and the symbol codes they are made of
+    int g_prefix = 0;
+    uint32_t g_share_lo = 0, g_share_hi = 0;
+    int g_bits = 0;
+    uint8_t g_code[256] = {0};
+    bool g_share_valid = false;
+};
+
+struct PfpState : PfpSummary {
+    bool have_parse = false;
     DevBuf<uint8_t> dict, ptab, pinfo;   // pinfo: 16-byte record per phrase (k_phrase_hash)  // ptab: 16-byte record per distinct phrase (phrase_table)
     DevBuf<uint16_t> tmask;             // trigger masks, one per 16 text positions
     DevBuf<uint32_t> tcnt, toff;        // triggers per workgroup of the trigger pass and their exclusive scan
@@ -42,9 +59,7 @@ struct PfpState {
     ParseLcp plcp;
     DevBuf<uint32_t> ghead, ce_hl, ce_slen, occ_sl, lcp_d;   // lcp_d: LCP array of the dictionary (suffix-array order)
     DevBuf<uint64_t> segmin;                                // (flag, minimum of lcp_d since the valid entry before) per entry
-    uint32_t n_entries = 0, n_fallback = 0, emit_launches = 0;
     std::unordered_map<uint64_t, uint64_t> first_tile;     // window begin (stream entry) -> first emitter tile of the window
-    bool bwt_ready = false;
     // the emitter between its windows (Engine::pfp_emit_window): arguments shared by every launch, the oversized groups'
     // offsets / begin positions on the host, the BWT code of their sort keys
     bool emit_ready = false;
@@ -63,13 +78,7 @@ struct PfpState {
     DevBuf<uint64_t> g_nxt;
     std::vector<uint64_t> g_bins, g_bins_rep;     // text suffixes per bin of leading characters; of them representatives (expansion)
     DevBuf<uint32_t> g_repbits;                   // bit k: phrase k is the representative occurrence of its distinct phrase
-    int g_prefix = 0;
     uint32_t g_nbins = 0;
-    // the bins the last stream of this producer took (a rank's share: Engine::set_scan_shard), and the symbol codes they are made of
-    uint32_t g_share_lo = 0, g_share_hi = 0;
-    int g_bits = 0;
-    uint8_t g_code[256] = {0};
-    bool g_share_valid = false;
     // giant phrases of the bucket-wise producer (guided.cpp::build_giant; gk::Ctx::g_*)
     DevBuf<uint32_t> gi_k, gi_base, gi_isa, gi_grp, gi_lcp, gi_bmin, gi_bits, gi_rank;
     DevBuf<uint64_t> gi_ps;

@@ -10,8 +10,6 @@
 
 namespace mmt {
 
-static int bit_width_u64(uint64_t v) { int b = 0; while (v) { b++; v >>= 1; } return b; }
-
 DoublingSorter::~DoublingSorter() {
     if (side_) (void)hipStreamDestroy(side_);
     if (ev_main_) (void)hipEventDestroy(ev_main_);

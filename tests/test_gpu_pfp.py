@@ -95,6 +95,51 @@ def test_parse_statistics_equal_the_oracles_parse(engine, wp):
     engine.set_producer("auto")
 
 
+@pytest.mark.parametrize("producer", ["pfp", "guided", "expand"])
+def test_summary_of_a_slim_run_equals_the_plain_runs(engine, producer):
+    """A slim run (MUMEMTO_LEAN: read in the constructor) gives the producer's tables back before the run ends; the counters,
+    the stage times and the bucket-wise share it reports afterwards must be the ones a plain run reports.
+
+    The parse proper writes all nine counters and all nine are compared.  The bucket-wise producer writes rounds_dict (the
+    rounds of its batches) but never the counters in NOT_WRITTEN: after it they hold what the engine's last run through the
+    parse proper left -- the entries of that run on the module's engine, 0 on the fresh one --, which says nothing about a slim
+    run, so they are left out for that producer."""
+    import mumemto_amd
+    docs = synth.pangenome(**CASES["indel_inv"])
+    want = O.run(docs).text()
+    NOT_WRITTEN = {"pfp": (), "guided": ("run_refined", "entries", "oversized_groups"),
+                   "expand": ("run_refined",)}["guided" if PACKED_TEXT and producer == "pfp" else producer]
+
+    def summary(e):
+        e.set_producer(producer, 6, 37)
+        e.set_docs(docs)
+        e.run()
+        assert e.output_text() == want
+        counts = e.pfp_counts()
+        assert len(counts) == 9
+        s = dict(counts={k: v for k, v in counts.items() if k not in NOT_WRITTEN}, used=e.producer_used(),
+                 expanded=e.producer_expanded(), stats=e.producer_stats())
+        assert e.pfp_stage_ms()[7] > 0
+        if producer != "pfp":
+            assert e.kmer_in_share(b"ACGT") is True
+        return s
+
+    plain = summary(engine)
+    engine.set_producer("auto")
+    os.environ["MUMEMTO_LEAN"] = "1"
+    try:
+        lean = mumemto_amd.Engine(0)
+    finally:
+        del os.environ["MUMEMTO_LEAN"]
+    try:
+        slim = summary(lean)
+    finally:
+        lean.close()
+    assert slim == plain
+    assert plain["used"] == ("pfp" if producer == "pfp" and not PACKED_TEXT else "guided")
+    assert plain["expanded"] == (producer == "expand")
+
+
 def test_degenerate_inputs_through_the_parse(engine):
     for docs in ([[b"A"], [b"A"]], [[b""], [b""]], [[b"ACGT" * 30], [b"ACGT" * 30]], [[b"A" * 3000], [b"A" * 2500]],
                  [[b"N" * 5000 + b"ACGTGGA" * 5], [b"ACGTGGA" * 5 + b"N" * 4000]]):
