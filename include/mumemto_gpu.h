@@ -454,6 +454,56 @@ MMT_API int mmt_merged_label_write_text(mmt_merged* m, const char* path);
  * + prefix sum, of the write, and of the copies to the host + the wait for the file; [4] cells, [5] absent cells, [6] columns
  * whose contig ends were searched in HBM rather than LDS, [7] bytes of the text as last measured.                       */
 MMT_API int mmt_merged_label_stats(const mmt_merged* m, double out[8]);
+/* ---- string-based merge, last step (`mumemto merge` without a common anchor: mumemto/merge_mums.py:211-307) ------------------
+ * Callers detect these entry points by their symbols; mmt_abi_version() did not change for them.
+ * The partitions were run with -M (PREFIX.thresh / .thresh_rev), their MUM strings extracted as `#`-terminated records
+ * (extract_mums) and the multi-MUMs of those collections found ("MUMs of MUMs", mom).  mmt_string_fold maps every row of mom
+ * back through the partitions' rows and merges the threshold tables, on the device; the closed form is
+ * mumemto_amd/merge_mums.py string_merge, and the results equal it byte for byte:
+ *   - a row of mom is cut at the `#` of collection 0 it spans; a piece shorter than 20 is dropped unless it is the whole row;
+ *   - in every partition i the piece lies in a record (the first whose end is beyond its start there); it survives when in every
+ *     partition that record exists and 0 != thresh_i[start] < the piece's length (indices clamped into the table);
+ *   - the row of a surviving piece has the columns of every partition in turn: the start of the record's row + the piece's
+ *     distance from the record's left end on a `+` cell, from its right end on a `-` cell, and the cell's strand, flipped when
+ *     the piece matched reversed in collection i; rows in ascending order of column 0, equal starts in the order of the pieces;
+ *   - thresholds per position of a row: the maximum over the partitions when all are > 0, else 0 (thresh_i and thresh_rev_i
+ *     change places for a partition whose piece matched reversed); one 0 follows every row.
+ * All arrays below are host arrays.  records holds, for collection i, the record lengths [begin[i], begin[i + 1]) as mom's
+ * .lengths file lists them (the last record of a collection is shorter than its row + 1: do not derive them from the rows).
+ * It refuses, rc 3 and a message, before anything is launched over the table at fault: S that is not mom's n_docs or
+ * records->n_collections ("input # of MUM files does not match merged MUM input file"); a table of 2^32 - 1 rows or more; 2^32 - 256
+ * pieces or more; a partition without columns; a negative record length; more records in collection i than rows in partition i;
+ * a start of -1 in a partition or in mom; a partition whose column 0 is not ascending; thresh_len that is not the sum of
+ * length + 1 over the partition's rows.  The engine stays usable after a refusal.
+ * *out is a merged result like any other (mmt_merged_get / _text / _write_text / _collinear ...; it carries no anchor
+ * thresholds) that also holds the two merged tables until a call that replaces its table (mmt_merged_collinear,
+ * mmt_merged_sort_like_direct).                                                                                          */
+typedef struct mmt_string_part {
+    uint64_t n_rows, n_docs;
+    const uint32_t* length;     /* n_rows                                         */
+    const int64_t*  starts;     /* n_rows * n_docs, rows in ascending order of column 0 */
+    const uint8_t*  strands;    /* 1 = '+'                                        */
+    const uint16_t* thresh;     /* thresh_len entries each; not read for mom      */
+    const uint16_t* thresh_rev;
+    uint64_t thresh_len;
+} mmt_string_part;
+typedef struct mmt_string_records {
+    uint64_t n_collections;
+    const uint64_t* begin;      /* n_collections + 1                              */
+    const int64_t*  length;     /* begin[n_collections] record lengths (MUM length + 1 for the `#`) */
+} mmt_string_records;
+MMT_API int mmt_string_fold(mmt_engine* e, const mmt_string_part* parts, size_t S, const mmt_string_part* mom,
+                            const mmt_string_records* mom_records, mmt_merged** out);
+/* entries of either merged threshold table: the sum of length + 1 over the merged rows; 0 for a result of another kind   */
+MMT_API uint64_t mmt_merged_string_thresh_len(const mmt_merged* m);
+/* host copies of the two tables; either may be null.  rc 3 when m carries none.                                          */
+MMT_API int mmt_merged_string_thresh(const mmt_merged* m, uint16_t* thresh, uint16_t* thresh_rev);
+/* the same two tables in HBM; owned by m                                                                                */
+MMT_API int mmt_merged_string_thresh_device(const mmt_merged* m, const uint16_t** thresh, const uint16_t** thresh_rev);
+/* Of the mmt_string_fold that made m: out[0..3] HIP-event milliseconds of split, locate and test, assemble + sort + permute,
+ * thresholds; [4] pieces the rows of mom were cut into, [5] pieces dropped as shorter than 20, [6] pieces dropped by a
+ * partition's records or thresholds, [7] merged rows.                                                                    */
+MMT_API int mmt_merged_string_fold_stats(const mmt_merged* m, double out[8]);
 /* Re-order merged rows into the order of a direct run (lexicographic by match
  * string) using the anchor suffix ranks of the engine's last run, whose
  * document 0 must be the anchor.                              */

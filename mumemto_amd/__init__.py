@@ -23,6 +23,7 @@ from .binding import (  # noqa: F401
     mum_to_bed,
     mumemto_mem,
     mumemto_mum,
+    string_merge_device,
 )
 
 __version__ = "0.1.0"

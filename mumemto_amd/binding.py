@@ -47,6 +47,15 @@ class Partition(C.Structure):  # mmt_partition (mumemto_gpu.h); thresh_bits 0 / 
                 ("thresh_on_device", C.c_uint8), ("rows_on_device", C.c_uint8), ("thresh_bits", C.c_uint8)]
 
 
+class StringPart(C.Structure):  # mmt_string_part (mumemto_gpu.h): host tables of a partition of the string-based merge
+    _fields_ = [("n_rows", C.c_uint64), ("n_docs", C.c_uint64), ("length", C.c_void_p), ("starts", C.c_void_p),
+                ("strands", C.c_void_p), ("thresh", C.c_void_p), ("thresh_rev", C.c_void_p), ("thresh_len", C.c_uint64)]
+
+
+class StringRecords(C.Structure):  # mmt_string_records (mumemto_gpu.h)
+    _fields_ = [("n_collections", C.c_uint64), ("begin", C.c_void_p), ("length", C.c_void_p)]
+
+
 class DevicePartition:
     """One partition's MUM rows and anchor thresholds as HBM addresses (what the multi-GPU exchange
     produces): length u32[n_rows], offsets i64[n_rows, n_docs], strands u8[n_rows, n_docs],
@@ -89,6 +98,8 @@ GPU_ABI_SYMBOLS = [
     "mmt_merged_bed_write_text", "mmt_merged_bed_stats",
     "mmt_merged_label", "mmt_merged_label_cells", "mmt_merged_label_cells_device", "mmt_merged_label_text",
     "mmt_merged_label_write_text", "mmt_merged_label_stats",
+    "mmt_string_fold", "mmt_merged_string_thresh", "mmt_merged_string_thresh_device", "mmt_merged_string_thresh_len",
+    "mmt_merged_string_fold_stats",
 ]
 
 
@@ -220,6 +231,13 @@ def load_library():
     L.mmt_merged_label_text.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
     L.mmt_merged_label_write_text.argtypes = [C.c_void_p, C.c_char_p]
     L.mmt_merged_label_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    L.mmt_string_fold.argtypes = [C.c_void_p, C.POINTER(StringPart), C.c_size_t, C.POINTER(StringPart), C.POINTER(StringRecords),
+                                  C.POINTER(C.c_void_p)]
+    L.mmt_merged_string_thresh_len.restype = C.c_uint64
+    L.mmt_merged_string_thresh_len.argtypes = [C.c_void_p]
+    L.mmt_merged_string_thresh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mmt_merged_string_thresh_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.mmt_merged_string_fold_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.mmt_comm_unique_id.argtypes = [C.c_void_p]
     L.mmt_comm_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
     L.mmt_comm_destroy.argtypes = [C.c_void_p]
@@ -852,6 +870,60 @@ class Merged:
         _check(engine.L.mmt_anchor_merge_min_len(engine.h, arr, len(parts), C.c_uint32(min_len), C.byref(m)))
         return cls(engine, m)
 
+    @classmethod
+    def string_fold(cls, engine, parts, mom, mom_records):
+        """the last step of the string-based merge on the device, with the inputs of merge_mums.string_merge: parts = per
+        partition (lengths u32 [n], starts i64 [n, c], strands [n, c], thresh u16 [T], thresh_rev u16 [T]), rows in the order
+        of their first column; mom = (lengths, starts [m, S], strands [m, S]) of the MUMs of MUMs; mom_records = per
+        collection the record lengths of mom's .lengths file.  The handle carries the merged rows and string_thresh()."""
+        keep = []
+
+        def table(rows, thresh=None, thresh_rev=None):
+            length = np.ascontiguousarray(rows[0], np.uint32)
+            starts = np.ascontiguousarray(rows[1], np.int64)
+            if starts.ndim != 2:
+                starts = starts.reshape(len(length), -1)
+            strands = np.ascontiguousarray(np.asarray(rows[2]).astype(np.uint8)).reshape(starts.shape)
+            th = np.ascontiguousarray(thresh if thresh is not None else [], np.uint16)
+            th_rev = np.ascontiguousarray(thresh_rev if thresh_rev is not None else [], np.uint16)
+            if len(th) != len(th_rev):
+                raise MumemtoError("string fold: thresh and thresh_rev of a partition differ in length (%d, %d)" % (len(th), len(th_rev)))
+            keep.extend([length, starts, strands, th, th_rev])
+            return StringPart(len(length), starts.shape[1], _p(length).value, _p(starts).value, _p(strands).value, _p(th).value,
+                              _p(th_rev).value, len(th))
+
+        arr = (StringPart * max(len(parts), 1))()
+        for i, part in enumerate(parts):
+            arr[i] = table(part[:3], part[3], part[4])
+        mom_part = table(mom)
+        begin = np.zeros(len(mom_records) + 1, np.uint64)
+        begin[1:] = np.cumsum([len(r) for r in mom_records], dtype=np.uint64)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(r, np.int64).ravel() for r in mom_records] + [np.zeros(1, np.int64)]))
+        records = StringRecords(len(mom_records), _p(begin).value, _p(flat).value)
+        m = C.c_void_p()
+        _check(engine.L.mmt_string_fold(engine.h, arr, len(parts), C.byref(mom_part), C.byref(records), C.byref(m)))
+        return cls(engine, m)
+
+    def string_thresh(self):
+        """(thresh u16, thresh_rev u16) of a string_fold: the positions of the rows in their order, a 0 behind every row"""
+        n = int(self.L.mmt_merged_string_thresh_len(self.h))
+        th, th_rev = np.zeros(max(n, 1), np.uint16), np.zeros(max(n, 1), np.uint16)
+        _check(self.L.mmt_merged_string_thresh(self.h, _p(th), _p(th_rev)))
+        return th[:n], th_rev[:n]
+
+    def string_thresh_device(self):
+        """(HBM address of thresh, of thresh_rev, entries of either); owned by the handle"""
+        a, b = C.c_void_p(), C.c_void_p()
+        _check(self.L.mmt_merged_string_thresh_device(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value, int(self.L.mmt_merged_string_thresh_len(self.h))
+
+    def string_fold_stats(self):
+        st = (C.c_double * 8)()
+        _check(self.L.mmt_merged_string_fold_stats(self.h, st))
+        d = {k: float(st[i]) for i, k in enumerate(["split_ms", "locate_ms", "assemble_ms", "thresholds_ms"])}
+        d.update(pieces=int(st[4]), dropped_short=int(st[5]), dropped_thresh=int(st[6]), rows=int(st[7]))
+        return d
+
     def close(self):
         if getattr(self, "h", None):
             self.L.mmt_merged_free(self.h)
@@ -1180,6 +1252,18 @@ def get_sequence_info(lengths, starts, strands, contigs, blocks=None, names=Fals
                 m.set_blocks(blocks)
             m.label(contigs, names)
             return m.label_cells() + (m.label_text(),)
+    finally:
+        eng.close()
+
+
+def string_merge_device(parts, mom, mom_records, device=0):
+    """merge_mums.string_merge on the device: the same inputs, the same five results (lengths u32, starts i64, strands bool,
+    thresh u16, thresh_rev u16)"""
+    eng = Engine(device)
+    try:
+        with Merged.string_fold(eng, parts, mom, mom_records) as m:
+            length, starts, strands = m.rows()
+            return (length, starts, strands.astype(bool)) + m.string_thresh()
     finally:
         eng.close()
 

@@ -23,6 +23,7 @@
 #include "collinear.hpp"
 #include "bed.hpp"
 #include "label.hpp"
+#include "string_fold.hpp"
 #include "coverage.hpp"
 #include "inversion.hpp"
 
@@ -111,6 +112,7 @@ struct mmt_merged {
     std::string bed_text;              // of the last mmt_merged_bed_text
     mmt::LabelStats label;             // of the last mmt_merged_label, and of the text written since
     std::string label_text;            // of the last mmt_merged_label_text
+    mmt::StringFoldStats sfold;        // of the mmt_string_fold that made the rows
 };
 
 extern "C" {
@@ -986,6 +988,47 @@ int mmt_merged_label_stats(const mmt_merged* m, double out[8]) {
     for (int i = 0; i < 4; i++) out[i] = S.ms[i];
     out[4] = (double)(has ? S.cells : 0); out[5] = (double)(has ? S.absent : 0); out[6] = (double)(has ? S.hbm_columns : 0);
     out[7] = (double)(has ? S.text_bytes : 0);
+    return 0;
+}
+// ---- string-based merge, last step (string_fold.cpp) -------------------------------------------
+int mmt_string_fold(mmt_engine* e, const mmt_string_part* parts, size_t S, const mmt_string_part* mom,
+                    const mmt_string_records* mom_records, mmt_merged** out) {
+    if (!e || !out) return fail(1, "engine and out must be non-null");
+    *out = nullptr;
+    MMT_TRY
+    std::unique_ptr<mmt_merged> m(new mmt_merged());
+    m->rows = mmt::string_fold(*e->e, parts, S, mom, mom_records, &m->sfold);
+    m->engine = e->e.get();
+    *out = m.release();
+    MMT_CATCH
+}
+uint64_t mmt_merged_string_thresh_len(const mmt_merged* m) { return m && m->rows.has_string_thresh ? m->rows.string_thresh_len : 0; }
+int mmt_merged_string_thresh(const mmt_merged* m, uint16_t* thresh, uint16_t* thresh_rev) {
+    if (!m) return fail(1, "null");
+    if (!m->rows.has_string_thresh) return fail(3, "no merged thresholds attached: the rows are not those of mmt_string_fold");
+    MMT_TRY
+    const size_t n = m->rows.string_thresh_len;
+    if (n) {
+        hipStream_t st = m->engine->stream();
+        MMT_HIP(hipSetDevice(m->engine->device()));
+        if (thresh) MMT_HIP(hipMemcpyAsync(thresh, m->rows.d_string_thresh.get(), n * 2, hipMemcpyDeviceToHost, st));
+        if (thresh_rev) MMT_HIP(hipMemcpyAsync(thresh_rev, m->rows.d_string_thresh_rev.get(), n * 2, hipMemcpyDeviceToHost, st));
+        MMT_HIP(hipStreamSynchronize(st));
+    }
+    MMT_CATCH
+}
+int mmt_merged_string_thresh_device(const mmt_merged* m, const uint16_t** thresh, const uint16_t** thresh_rev) {
+    if (!m) return fail(1, "null");
+    if (!m->rows.has_string_thresh) return fail(3, "no merged thresholds attached: the rows are not those of mmt_string_fold");
+    if (thresh) *thresh = m->rows.d_string_thresh.get();
+    if (thresh_rev) *thresh_rev = m->rows.d_string_thresh_rev.get();
+    return 0;
+}
+int mmt_merged_string_fold_stats(const mmt_merged* m, double out[8]) {
+    if (!m || !out) return fail(1, "null");
+    const mmt::StringFoldStats& S = m->sfold;
+    for (int i = 0; i < 4; i++) out[i] = S.ms[i];
+    out[4] = (double)S.pieces; out[5] = (double)S.dropped_short; out[6] = (double)S.dropped_thresh; out[7] = (double)S.rows;
     return 0;
 }
 int mmt_merged_sort_like_direct(mmt_engine* e, mmt_merged* m) {

@@ -51,6 +51,11 @@ struct MergedRows {
     DevBuf<uint64_t> d_label_contig_begin;    // n_docs + 1: the contigs of column c among all contigs
     DevBuf<uint64_t> d_label_name_begin;      // per contig (and one more): its name in d_label_names (with label_names)
     DevBuf<char> d_label_names;
+    // merged thresh / thresh_rev of a string fold (string_fold.hpp): the positions of the rows in their order, a 0 behind every
+    // row; whatever replaces the table or its order drops them
+    bool has_string_thresh = false;
+    size_t string_thresh_len = 0;
+    DevBuf<uint16_t> d_string_thresh, d_string_thresh_rev;
 
     MergedRows() = default;
     MergedRows(MergedRows&&) noexcept = default;
@@ -61,7 +66,10 @@ struct MergedRows {
     // new blocks (collinear_blocks, set_blocks): calls and BED records go, coverage and labels stay
     void blocks_replaced() { has_calls = false; n_calls = 0; has_bed = false; }
     // a new table or row order (sort_like_direct, collinear_blocks): everything attached goes
-    void table_replaced() { has_blocks = false; n_blocks = 0; blocks_replaced(); has_coverage = false; has_label = false; }
+    void table_replaced() {
+        has_blocks = false; n_blocks = 0; blocks_replaced(); has_coverage = false; has_label = false;
+        has_string_thresh = false; string_thresh_len = 0;
+    }
 };
 
 }  // namespace mmt

@@ -80,4 +80,15 @@ __device__ __forceinline__ uint32_t upper_bound(const int64_t* ends, uint32_t cn
     return lo;
 }
 
+// the last i in [0, n) with at(i) <= v, for an ascending at with at(0) <= v (rows by their first position: row 0 begins at 0)
+template <typename At>
+__device__ __forceinline__ uint32_t last_at_or_before(uint32_t n, uint64_t v, At at) {
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (at(mid) <= v) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
 }}  // namespace mmt::tt

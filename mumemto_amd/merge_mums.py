@@ -7,7 +7,8 @@ Host-side twin of the reference's merge driver (mumemto/merge_mums.py; command l
 * every PREFIX.thresh present   -> string-based merge:
     1. `extract_mums` writes each partition's MUM strings as a multi-FASTA, one `#`-terminated record per row;
     2. `mumemto_exec` (the GPU hot path) finds the multi-MUMs of those collections ("MUMs of MUMs");
-    3. `string_merge` below maps every such match back through the partitions' rows and thresholds.
+    3. `string_merge` below maps every such match back through the partitions' rows and thresholds; with `--device`
+       (an addition) the library's string fold does, in HBM (csrc/string_fold.cpp, held to `string_merge` byte for byte).
 
 Step 3 is the reference's per-row Python loop (merge_mums.py:226-287) restated over whole NumPy columns; inputs and
 outputs are the same files, byte for byte (tests/golden/string_merge holds the reference's own outputs).
@@ -37,6 +38,8 @@ def parse_arguments(argv=None):
     ap.add_argument("mum_files", metavar="MUM_FILES", nargs="+", help="Paths to MUMs files to merge")
     ap.add_argument("--output", "-o", help="Path to output merged MUMs file", default="merged")
     ap.add_argument("--verbose", "-v", action="store_true", help="Print verbose output")
+    ap.add_argument("--device", action="store_true",
+                    help="Run the last step of a string merge (rows and thresholds) on the GPU as well (MUMEMTO_DEVICE chooses it)")
     args = ap.parse_args(argv)
     if len(args.mum_files) < 2:
         ap.error("At least two MUMs files are required for merging")
@@ -258,6 +261,25 @@ def sort_partition(prefix, out_prefix=None):
     mumsio.write_mums((out_prefix or prefix) + ".mums", lengths, starts, strands)
 
 
+def write_merged_on_device(args, parts, mom, mom_records):
+    """step 3 through the library's string fold (csrc/string_fold.cpp): the rows stay in HBM, the .mums bytes are formatted
+    there; a .bumbl and the threshold files are written from the downloaded arrays.  -> (rows, thresh, thresh_rev)"""
+    from . import binding
+    eng = binding.Engine(int(os.environ.get("MUMEMTO_DEVICE", "0")))
+    try:
+        with binding.Merged.string_fold(eng, parts, mom, mom_records) as m:
+            if args.verbose:
+                print("string fold on the device: %s" % m.string_fold_stats(), file=sys.stderr)
+            if args.output.endswith(".bumbl"):
+                lengths, starts, strands = m.rows()
+                mumsio.write_bumbl(args.output, lengths, starts, strands.astype(bool))
+            else:
+                m.write_text(args.output)
+            return (m.n_rows,) + m.string_thresh()
+    finally:
+        eng.close()
+
+
 def main(args):
     if all(os.path.exists(p + ".athresh") for p in args.paths):
         if args.merged_mums is not None:
@@ -277,12 +299,16 @@ def main(args):
         rows = _sorted_by_first_offset(mumsio.read_rows(f))
         parts.append(rows + (np.fromfile(p + ".thresh", np.uint16), np.fromfile(p + ".thresh_rev", np.uint16)))
     mom_prefix = os.path.splitext(args.merged_mums)[0]
-    lengths, starts, strands, thresh, thresh_rev = string_merge(parts, mumsio.read_mums(args.merged_mums),
-                                                                record_lengths(mom_prefix + ".lengths"))
-    if args.output.endswith(".bumbl"):
-        mumsio.write_bumbl(args.output, lengths, starts, strands)
+    mom, mom_records = mumsio.read_mums(args.merged_mums), record_lengths(mom_prefix + ".lengths")
+    if args.device:
+        n_rows, thresh, thresh_rev = write_merged_on_device(args, parts, mom, mom_records)
     else:
-        mumsio.write_mums(args.output, lengths, starts, strands)
+        lengths, starts, strands, thresh, thresh_rev = string_merge(parts, mom, mom_records)
+        n_rows = len(lengths)
+        if args.output.endswith(".bumbl"):
+            mumsio.write_bumbl(args.output, lengths, starts, strands)
+        else:
+            mumsio.write_mums(args.output, lengths, starts, strands)
     thresh.tofile(args.output_base + ".thresh")
     thresh_rev.tofile(args.output_base + ".thresh_rev")
     if cleanup:
@@ -290,7 +316,7 @@ def main(args):
             os.remove(p + "_mums.fa")
         os.remove(args.merged_mums)
         os.remove(args.output_base + "_temp_merged.lengths")
-    return len(lengths)
+    return n_rows
 
 
 if __name__ == "__main__":
