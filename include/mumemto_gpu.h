@@ -380,6 +380,45 @@ MMT_API int mmt_merged_coverage_runs_device(const mmt_merged* m, const uint64_t*
 /* Of the last mmt_merged_coverage on m: out[0..3] HIP-event milliseconds of the extraction, column sorts, running maximum +
  * sum, runs; [4] columns that needed a sort, [5] columns found ascending, [6] column batches, [7] runs in all.           */
 MMT_API int mmt_merged_coverage_stats(const mmt_merged* m, double out[8]);
+/* ---- MEM density (`mumemto/mem_density.py`) ---------------------------------------------------------------------------------
+ * Callers detect these entry points by their symbols; mmt_abi_version() did not change for them.
+ * How many multi-MEM occurrences cover each position of each sequence, summed over bins of bin_width positions.  With
+ * size = the maximum of seq_lengths, an occurrence (doc, start) of a row of length l adds 1 to the positions of doc that the
+ * numpy slice start : start + l selects on an axis of `size` entries (the reference's `coverage[idx, start:start+l] += 1`):
+ *   a = start < 0 ? max(start + size, 0) : min(start, size),  b = the same rule for start + l,  [a, b) when a < b, else nothing.
+ * So the cut is at `size`, not at the sequence's own length, a negative start wraps as numpy wraps it (start -30, l 25 on
+ * size 100 covers [70, 95); start -1, l 30 covers nothing), and strands play no part.  Bin k covers [k W, min((k + 1) W, size)),
+ * nbins = ceil(size / W), and the result is the num x nbins table of the depths summed over each bin: exact 64-bit integers,
+ * for W = 1 the reference's array.  A bin_width beyond size is taken as size (one bin per sequence).
+ *
+ * mmt_density_create makes the zeroed tables on e's device (24 x num x nbins bytes).  mmt_density_add_rows takes a host batch of
+ * whole rows -- length[n_rows], occ_start[n_rows + 1] from 0, offsets and seq_ids[occ_start[n_rows]], the shape of mmt_rows_mem --
+ * and may be called any number of times; mmt_density_add_engine adds the MEM rows of e's last run where they lie in HBM.
+ * mmt_density_finish makes the table from everything added so far; adding after it goes on from what is there, so a caller can
+ * read intermediate results (the accessors return rc 3 between an add and the next finish).  Every refusal is rc 3 and a message,
+ * is decided before anything is launched and leaves the engine and the tables as they were: a null seq_lengths or null row
+ * tables; num == 0; a length <= 0 (or beyond 2^40); bin_width == 0; tables that exceed what the device heap can give (the
+ * message names the smallest bin width that fits); a seq_id >= num (the message names the first such row; the reference raises
+ * IndexError); occ_start that does not begin at 0, is not ascending or ends beyond 2^40; mmt_density_add_engine after a
+ * MUM-mode run, after a run whose text sink dropped the rows window by window, or with num different from the run's
+ * documents.  A batch without rows or occurrences is legal.                                                                  */
+typedef struct mmt_density mmt_density;
+MMT_API int mmt_density_create(mmt_engine* e, const int64_t* seq_lengths, size_t num, uint64_t bin_width, mmt_density** out);
+MMT_API void mmt_density_free(mmt_density* d);
+MMT_API int mmt_density_add_rows(mmt_density* d, const uint32_t* length, const uint64_t* occ_start, const int64_t* offsets,
+                                 const uint64_t* seq_ids, size_t n_rows);
+MMT_API int mmt_density_add_engine(mmt_density* d, mmt_engine* e);
+MMT_API int mmt_density_finish(mmt_density* d);
+/* out[0] num, [1] nbins, [2] size, [3] the bin width in use                                                                */
+MMT_API int mmt_density_shape(const mmt_density* d, uint64_t out[4]);
+/* bins receives num x nbins host entries, row-major                                                                       */
+MMT_API int mmt_density_bins(const mmt_density* d, uint64_t* bins);
+/* the same table in HBM; owned by d, rewritten by the next mmt_density_finish                                              */
+MMT_API int mmt_density_bins_device(const mmt_density* d, const uint64_t** bins);
+/* out[0] HIP-event milliseconds of every add pass so far, [1] of the last finish pass; counted over every add: [2]
+ * occurrences, [3] occurrences with start + l beyond size (cut there), [4] occurrences that covered nothing, [5] occurrences
+ * with a negative start; [6] nbins, [7] the bin width in use.                                                              */
+MMT_API int mmt_density_stats(const mmt_density* d, double out[8]);
 /* ---- BED intervals (`mumemto bed`: mumemto/mum_to_bed.py) -----------------------------------------------------------------
  * Callers detect these entry points by their symbols; mmt_abi_version() did not change for them.
  * The collinear blocks and the long multi-MUMs of the table as `contig <TAB> start <TAB> end <TAB> name <TAB> strand` lines in

@@ -8,6 +8,7 @@ usable, calls raise.
 """
 from .binding import (  # noqa: F401
     Comm,
+    Density,
     DevicePartition,
     Engine,
     Merged,
@@ -19,6 +20,7 @@ from .binding import (  # noqa: F401
     get_sequence_info,
     library_path,
     load_library,
+    mem_density,
     mum_coverage,
     mum_to_bed,
     mumemto_mem,

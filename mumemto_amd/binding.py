@@ -100,6 +100,8 @@ GPU_ABI_SYMBOLS = [
     "mmt_merged_label_write_text", "mmt_merged_label_stats",
     "mmt_string_fold", "mmt_merged_string_thresh", "mmt_merged_string_thresh_device", "mmt_merged_string_thresh_len",
     "mmt_merged_string_fold_stats",
+    "mmt_density_create", "mmt_density_free", "mmt_density_add_rows", "mmt_density_add_engine", "mmt_density_finish",
+    "mmt_density_shape", "mmt_density_bins", "mmt_density_bins_device", "mmt_density_stats",
 ]
 
 
@@ -238,6 +240,16 @@ def load_library():
     L.mmt_merged_string_thresh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.mmt_merged_string_thresh_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.mmt_merged_string_fold_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    L.mmt_density_create.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.POINTER(C.c_void_p)]
+    L.mmt_density_free.argtypes = [C.c_void_p]
+    L.mmt_density_free.restype = None
+    L.mmt_density_add_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    L.mmt_density_add_engine.argtypes = [C.c_void_p, C.c_void_p]
+    L.mmt_density_finish.argtypes = [C.c_void_p]
+    L.mmt_density_shape.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mmt_density_bins.argtypes = [C.c_void_p, C.c_void_p]
+    L.mmt_density_bins_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.mmt_density_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.mmt_comm_unique_id.argtypes = [C.c_void_p]
     L.mmt_comm_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
     L.mmt_comm_destroy.argtypes = [C.c_void_p]
@@ -1198,6 +1210,109 @@ def mum_coverage(lengths, starts, strands, seq_lengths, seq_idx=None, min_length
         with Merged.from_rows(eng, lengths, starts, strands) as m:
             covered = m.coverage(seq_lengths, seq_idx, min_length)
             return (covered,) + m.coverage_runs()
+    finally:
+        eng.close()
+
+
+class Density:
+    """The MEM density of the sequences in the HBM of an engine's GPU (mmt_density of mumemto_gpu.h): how many multi-MEM
+    occurrences cover each position, summed over bins of bin_width positions -- with bin_width 1 the array of the reference's
+    mem_density.py.  Rows are added from host batches (add_rows) or from the engine's last MEM-mode run where they lie
+    (add_engine), any number of times; finish() makes the table, bins() reads it, and adding goes on afterwards."""
+
+    def __init__(self, engine, seq_lengths, bin_width=1):
+        self.engine, self.L = engine, engine.L
+        lens = np.ascontiguousarray(seq_lengths, np.int64).ravel()
+        if int(bin_width) < 0:
+            raise MumemtoError("mem density: a negative bin width (%d)" % int(bin_width))
+        h = C.c_void_p()
+        _check(self.L.mmt_density_create(engine.h, _p(lens), len(lens), int(bin_width), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.mmt_density_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def shape(self):
+        """(num, nbins, size, the bin width in use)"""
+        out = (C.c_uint64 * 4)()
+        _check(self.L.mmt_density_shape(self.h, out))
+        return tuple(int(v) for v in out)
+
+    def add_rows(self, lengths, occ_start, starts, docs):
+        """a batch of whole rows: lengths u32 [n], occ_start u64 [n + 1] from 0, starts i64 and docs u64 [occ_start[n]]"""
+        lengths = np.ascontiguousarray(lengths, np.uint32)
+        occ_start = np.ascontiguousarray(occ_start, np.uint64)
+        starts = np.ascontiguousarray(starts, np.int64)
+        docs = np.ascontiguousarray(docs, np.uint64)
+        if len(occ_start) != len(lengths) + 1:
+            raise MumemtoError("mem density: occ_start has %d entries for %d rows (one more is needed)" % (len(occ_start), len(lengths)))
+        if len(starts) != len(docs) or len(starts) < int(occ_start[-1]):
+            raise MumemtoError("mem density: %d starts and %d documents for %d occurrences" % (len(starts), len(docs), int(occ_start[-1])))
+        _check(self.L.mmt_density_add_rows(self.h, _p(lengths), _p(occ_start), _p(starts), _p(docs), len(lengths)))
+
+    def add_engine(self, engine=None):
+        """the MEM rows of the last run of `engine` (default: the engine the tables live on), read in HBM"""
+        _check(self.L.mmt_density_add_engine(self.h, (engine or self.engine).h))
+
+    def finish(self):
+        _check(self.L.mmt_density_finish(self.h))
+
+    def bins(self):
+        """uint64 [num, nbins]: the depth summed over every bin, after finish()"""
+        num, nbins = self.shape[:2]
+        out = np.zeros((num, nbins), np.uint64)
+        _check(self.L.mmt_density_bins(self.h, _p(out)))
+        return out
+
+    def bins_device(self):
+        """(HBM address of the uint64 [num, nbins] table, num, nbins); owned by the handle, rewritten by the next finish()"""
+        a = C.c_void_p()
+        _check(self.L.mmt_density_bins_device(self.h, C.byref(a)))
+        return (a.value,) + self.shape[:2]
+
+    def stats(self):
+        st = (C.c_double * 8)()
+        _check(self.L.mmt_density_stats(self.h, st))
+        d = dict(add_ms=float(st[0]), finish_ms=float(st[1]))
+        d.update(occurrences=int(st[2]), cut=int(st[3]), empty=int(st[4]), negative=int(st[5]), nbins=int(st[6]), bin_width=int(st[7]))
+        return d
+
+
+def _engine_mem_density(self, seq_lengths, bin_width=1):
+    """uint64 [n_docs, nbins]: the density of the MEM rows of this engine's last run, from where they lie in HBM"""
+    with Density(self, seq_lengths, bin_width) as d:
+        d.add_engine()
+        d.finish()
+        return d.bins()
+
+
+Engine.mem_density = _engine_mem_density
+
+
+def mem_density(lengths, occ_start, starts, docs, seq_lengths, bin_width=1, device=0):
+    """MEM rows on the host (the arrays of Engine.rows_mem, or a batch of mumsio.read_mems) -> uint64 [num, nbins]: the number
+    of occurrences that cover each position of each sequence, summed over bins of bin_width positions."""
+    eng = Engine(device)
+    try:
+        with Density(eng, seq_lengths, bin_width) as d:
+            d.add_rows(lengths, occ_start, starts, docs)
+            d.finish()
+            return d.bins()
     finally:
         eng.close()
 

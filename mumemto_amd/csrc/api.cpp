@@ -25,6 +25,7 @@
 #include "label.hpp"
 #include "string_fold.hpp"
 #include "coverage.hpp"
+#include "density.hpp"
 #include "inversion.hpp"
 
 namespace {
@@ -99,6 +100,9 @@ struct mmt_comm {
     mmt::Comm* c = nullptr;
     int rank = 0;
     std::string text;                  // rank 0: the gathered output of the last mmt_dist_gather_text
+};
+struct mmt_density {
+    std::unique_ptr<mmt::Density> d;
 };
 struct mmt_merged {
     mmt::MergedRows rows;
@@ -877,6 +881,62 @@ int mmt_merged_coverage_stats(const mmt_merged* m, double out[8]) {
     for (int i = 0; i < 4; i++) out[i] = S.ms[i];
     out[4] = (double)S.cols_sorted; out[5] = (double)S.cols_ascending; out[6] = (double)S.batches;
     out[7] = (double)(m->rows.has_coverage ? m->rows.cov_run_begin.back() : 0);
+    return 0;
+}
+// ---- MEM density (density.cpp) ---------------------------------------------------------------
+int mmt_density_create(mmt_engine* e, const int64_t* seq_lengths, size_t num, uint64_t bin_width, mmt_density** out) {
+    if (!out) return fail(1, "out must be non-null");
+    *out = nullptr;
+    if (!e) return fail(1, "engine must be non-null");
+    MMT_TRY
+    std::unique_ptr<mmt_density> d(new mmt_density());
+    d->d.reset(new mmt::Density(*e->e, seq_lengths, num, bin_width));
+    *out = d.release();
+    MMT_CATCH
+}
+void mmt_density_free(mmt_density* d) { delete d; }
+int mmt_density_add_rows(mmt_density* d, const uint32_t* length, const uint64_t* occ_start, const int64_t* offsets,
+                         const uint64_t* seq_ids, size_t n_rows) {
+    if (!d) return fail(1, "null");
+    MMT_TRY
+    d->d->add_rows(length, occ_start, offsets, seq_ids, n_rows);
+    MMT_CATCH
+}
+int mmt_density_add_engine(mmt_density* d, mmt_engine* e) {
+    if (!d || !e) return fail(1, "null");
+    MMT_TRY
+    d->d->add_engine(*e->e);
+    MMT_CATCH
+}
+int mmt_density_finish(mmt_density* d) {
+    if (!d) return fail(1, "null");
+    MMT_TRY
+    d->d->finish();
+    MMT_CATCH
+}
+int mmt_density_shape(const mmt_density* d, uint64_t out[4]) {
+    if (!d || !out) return fail(1, "null");
+    out[0] = d->d->num(); out[1] = d->d->nbins(); out[2] = (uint64_t)d->d->size(); out[3] = d->d->bin_width();
+    return 0;
+}
+int mmt_density_bins(const mmt_density* d, uint64_t* bins) {
+    if (!d) return fail(1, "null");
+    MMT_TRY
+    d->d->copy_bins(bins);
+    MMT_CATCH
+}
+int mmt_density_bins_device(const mmt_density* d, const uint64_t** bins) {
+    if (!d || !bins) return fail(1, "null");
+    if (!d->d->finished()) return fail(3, "mem density: no table yet: call mmt_density_finish after the last add");
+    *bins = d->d->bins_device();
+    return 0;
+}
+int mmt_density_stats(const mmt_density* d, double out[8]) {
+    if (!d || !out) return fail(1, "null");
+    const mmt::DensityStats& S = d->d->stats();
+    out[0] = S.ms[0]; out[1] = S.ms[1];
+    out[2] = (double)S.occurrences; out[3] = (double)S.cut; out[4] = (double)S.empty; out[5] = (double)S.negative;
+    out[6] = (double)d->d->nbins(); out[7] = (double)d->d->bin_width();
     return 0;
 }
 // ---- BED intervals (bed.cpp) ----------------------------------------------------------------

@@ -147,6 +147,13 @@ public:
         if (merged_thresh_valid_) { *len = merged_.d_length.get(); *off = merged_.d_offsets.get(); *st = merged_.d_strands.get(); }
         else { *len = d_olen_.get(); *off = d_ooffs_.get(); *st = d_ost_.get(); }
     }
+    // the MEM-mode rows of the last run as they sit in HBM (valid until the next run): lengths and first occurrences of the
+    // n_rows rows (no closing entry: the list ends at n_occ), starts and documents of the n_occ occurrences
+    void rows_mem_device(const uint32_t** len, const uint64_t** occ_start, const int64_t** off, const uint64_t** docs) const {
+        *len = d_olen_.get(); *occ_start = d_ooff_.get(); *off = d_ooffs_.get(); *docs = d_omdoc_.get();
+    }
+    // the last run's rows left the device window by window with the text sink (make_rows): only the file and the count remain
+    bool rows_left_device() const { return sink_discarded_ && !sink_written_path_.empty(); }
     bool last_run_partitioned() const { return merged_thresh_valid_; }
     // SA/LCP/BWT producer: 0 = automatic, 1 = direct suffix sort of the text (A8), 2 = prefix-free parsing (A2-A4),
     // 3 = prefix-free parsing without the dictionary's suffix array (guided.cpp; automatic when that would not fit)

@@ -1,6 +1,7 @@
 // table_text.hpp -- device helpers of every kernel that writes table text or looks a position up among contigs: decimals,
 // wave sums, the comma-separated fields of a merged-table line, the search over a column's contig ends.  Included by
-// rows_kernels.hip, merge_kernels.hip, label_kernels.hip and bed_kernels.hip after <hip/hip_runtime.h>.
+// rows_kernels.hip, merge_kernels.hip, label_kernels.hip, bed_kernels.hip and density_kernels.hip (wave sums, the row of a
+// position) after <hip/hip_runtime.h>.
 #pragma once
 #include <cstdint>
 
