@@ -189,6 +189,9 @@ MMT_API int mmt_column_bytes(const mmt_engine* e, uint32_t out[3]);
  * include/parse.hpp:45; dumps include/pfp_lcp_mum.hpp:323-369): the suffix-array column is stored as low word + high
  * byte, and the stream is scanned in ranges of suffix-array positions (mmt_scan_ranges of them in the last run).     */
 MMT_API int mmt_is_wide(const mmt_engine* e);
+/* the layout of the resident text (what mmt_merged_sequences reads): 1 = two bits per base and exception runs, 0 = a byte per base,
+ * -1 = the engine holds no text                                                                                          */
+MMT_API int mmt_engine_text_packed(const mmt_engine* e);
 MMT_API size_t mmt_scan_ranges(const mmt_engine* e);
 MMT_API int mmt_copy_sa64(const mmt_engine* e, uint64_t* out);    /* n entries, any text size */
 /* mmt_engine_set_stream_host for streams with 40-bit suffix-array entries (sa_hi = bits 32..39)                        */
@@ -493,6 +496,49 @@ MMT_API int mmt_merged_label_write_text(mmt_merged* m, const char* path);
  * + prefix sum, of the write, and of the copies to the host + the wait for the file; [4] cells, [5] absent cells, [6] columns
  * whose contig ends were searched in HBM rather than LDS, [7] bytes of the text as last measured.                       */
 MMT_API int mmt_merged_label_stats(const mmt_merged* m, double out[8]);
+/* ---- multi-MUM sequences (`extract_mums`: src/extract_mums.cpp, mumemto/extract_mums.py) --------------------------------------
+ * Callers detect these entry points by their symbols; mmt_abi_version() did not change for them.
+ * The bases of the rows of column col as a multi-FASTA, measured and formatted on the device.  Record i, i = the row's index
+ * in table order, is `>mum_<i>\n`, the bases, `#` unless terminator is 0, and the record separator.  The two forms of the
+ * reference are two dialects:
+ *   mmt_seq_binary (src/extract_mums.cpp): bytes as they are; strands ignored, always the forward slice; every record ends in
+ *     \n; a row without a start in col (-1) or with a start beyond the document's end is refused;
+ *   mmt_seq_python (mumemto/extract_mums.py): bases upper-cased; rows on '-' reverse-complemented (A<->T, C<->G, M<->K, R<->Y,
+ *     V<->B, H<->D, every other byte unchanged); records joined by \n, none behind the last; a row without a start or with a
+ *     start beyond the end is an empty record.
+ * In both a row that runs over the document's end is cut there and one that starts exactly at the end is an empty record.
+ *
+ * Three sources: mmt_merged_sequences reads the engine's own text after a run (one byte per base or packed; always upper
+ * case), where the table's columns are the engine's documents; mmt_merged_sequences_host takes the n_bases bases of document
+ * col from the host; mmt_merged_sequences_file reads them from a FASTA file, plain or gzip, records concatenated (n_bases,
+ * may be null, receives their number).  text_bytes (may be null) receives the length of the text.
+ * They read the table and change nothing of it: rows, blocks, inversion calls, coverage, BED records and labels stay; a table
+ * without rows gives an empty text.  They refuse, rc 3 and a message: col outside [0, n_docs), a start below -1, 2^32 rows or
+ * more, null bases with n_bases > 0, an unknown dialect, a resident source when the engine holds no text or has another number
+ * of documents than the table has columns, and the dialect's refusals, naming the first such row.  After a refused call no
+ * sequences are attached, those of an earlier call included.  Calling one again replaces the results; mmt_merged_collinear
+ * and mmt_merged_sort_like_direct drop them.  Before them the accessors below return rc 3 (null for the text).            */
+enum mmt_seq_dialect { mmt_seq_binary = 0, mmt_seq_python = 1 };
+MMT_API int mmt_merged_sequences(mmt_engine* e, mmt_merged* m, int64_t col, int dialect, int terminator, uint64_t* text_bytes);
+MMT_API int mmt_merged_sequences_host(mmt_engine* e, mmt_merged* m, const uint8_t* bases, uint64_t n_bases, int64_t col,
+                                      int dialect, int terminator, uint64_t* text_bytes);
+MMT_API int mmt_merged_sequences_file(mmt_engine* e, mmt_merged* m, const char* fasta_path, int64_t col, int dialect,
+                                      int terminator, uint64_t* n_bases, uint64_t* text_bytes);
+/* offsets receives n_rows + 1 host entries: record i is bytes [offsets[i], offsets[i + 1]) of the text                   */
+MMT_API int mmt_merged_sequences_offsets(const mmt_merged* m, uint64_t* offsets);
+/* the same array in HBM; owned by m                                                                                     */
+MMT_API int mmt_merged_sequences_offsets_device(const mmt_merged* m, const uint64_t** offsets);
+/* The text of the last mmt_merged_sequences*, formatted on the device; the bytes live until the next call on m.  Null (and a
+ * message) when no sequences are attached, or when the engine has laid out a text again (a run, a text or a stream handed
+ * over) since a resident call: the records are then measured anew.                                                       */
+MMT_API const char* mmt_merged_sequences_text(mmt_merged* m, size_t* len);
+/* The same bytes, formatted and written in pieces of whole records, to PATH.tmp, renamed to PATH when complete (a path that is
+ * no regular file, such as /dev/stdout, is written as it is).                                                            */
+MMT_API int mmt_merged_sequences_write_text(mmt_merged* m, const char* path);
+/* Of the last mmt_merged_sequences* on m and of the text asked for since: out[0] HIP-event milliseconds of measure + prefix
+ * sum, [1] of the format kernel; [2] records, [3] bases written, [4] rows cut at the document's end, [5] empty records,
+ * [6] bytes of the text, [7] pieces formatted since.                                                                     */
+MMT_API int mmt_merged_sequences_stats(const mmt_merged* m, double out[8]);
 /* ---- string-based merge, last step (`mumemto merge` without a common anchor: mumemto/merge_mums.py:211-307) ------------------
  * Callers detect these entry points by their symbols; mmt_abi_version() did not change for them.
  * The partitions were run with -M (PREFIX.thresh / .thresh_rev), their MUM strings extracted as `#`-terminated records

@@ -16,6 +16,7 @@ from .binding import (  # noqa: F401
     collinear_blocks,
     Params,
     exchange_digest,
+    extract_mums,
     find_inversions,
     get_sequence_info,
     library_path,

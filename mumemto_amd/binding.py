@@ -233,6 +233,18 @@ def load_library():
     L.mmt_merged_label_text.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
     L.mmt_merged_label_write_text.argtypes = [C.c_void_p, C.c_char_p]
     L.mmt_merged_label_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    L.mmt_merged_sequences.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+    L.mmt_engine_text_packed.argtypes = [C.c_void_p]
+    L.mmt_merged_sequences_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int64, C.c_int, C.c_int,
+                                            C.POINTER(C.c_uint64)]
+    L.mmt_merged_sequences_file.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int64, C.c_int, C.c_int,
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.mmt_merged_sequences_offsets.argtypes = [C.c_void_p, C.c_void_p]
+    L.mmt_merged_sequences_offsets_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.mmt_merged_sequences_text.restype = C.c_void_p
+    L.mmt_merged_sequences_text.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
+    L.mmt_merged_sequences_write_text.argtypes = [C.c_void_p, C.c_char_p]
+    L.mmt_merged_sequences_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.mmt_string_fold.argtypes = [C.c_void_p, C.POINTER(StringPart), C.c_size_t, C.POINTER(StringPart), C.POINTER(StringRecords),
                                   C.POINTER(C.c_void_p)]
     L.mmt_merged_string_thresh_len.restype = C.c_uint64
@@ -833,7 +845,8 @@ class Merged:
     """A row table in the HBM of an engine's GPU (mmt_merged of mumemto_gpu.h): the result of a fold, or rows handed over
     with Merged.from_rows / Merged.from_device.  collinear() computes the collinear blocks of its rows on the device,
     inversions() the inversion calls over them, coverage() the share of every sequence its rows cover, bed() the blocks and
-    rows as BED intervals in contig coordinates, label() every start as (contig, offset inside it)."""
+    rows as BED intervals in contig coordinates, label() every start as (contig, offset inside it), sequences() the rows' bases
+    as a multi-FASTA."""
 
     def __init__(self, engine, handle):
         self.engine, self.L, self.h = engine, engine.L, handle
@@ -1167,6 +1180,65 @@ class Merged:
         d.update(cells=int(st[4]), absent=int(st[5]), hbm_columns=int(st[6]), text_bytes=int(st[7]))
         return d
 
+    def sequences(self, col, source=None, dialect="python", terminator=True):
+        """Measures the multi-FASTA of the rows' bases in column col: record i is `>mum_<i>`, the bases of row i, `#` with
+        terminator.  source: None -- the engine's own text after a run (the table's columns are its documents); bytes, a
+        bytearray or a uint8 array -- the bases of document col; a str or os.PathLike -- a FASTA file of it, plain or gzip.
+        dialect: "binary" (the reference's extract_mums binary: bytes as they are, strands ignored, every record ends in a
+        newline, partial rows and starts beyond the end refused) or "python" (its extract_mums.py: upper case, rows on '-'
+        reverse-complemented, records joined by newlines, such rows empty).  Returns the length of the text; the table is
+        only read."""
+        self.sequences_doc_bases = None                    # (set by a FASTA path alone)
+        d = SEQ_DIALECTS.get(dialect, dialect)
+        if d not in (0, 1):
+            raise MumemtoError("sequences: unknown dialect %r (binary or python)" % (dialect,))
+        k = C.c_uint64()
+        col, term = C.c_int64(int(col)), C.c_int(1 if terminator else 0)
+        if source is None:
+            _check(self.L.mmt_merged_sequences(self.engine.h, self.h, col, d, term, C.byref(k)))
+        elif isinstance(source, (str, os.PathLike)):
+            nb = C.c_uint64()
+            _check(self.L.mmt_merged_sequences_file(self.engine.h, self.h, os.fsencode(source), col, d, term, C.byref(nb),
+                                                    C.byref(k)))
+            self.sequences_doc_bases = int(nb.value)       # the bases the file held
+        else:
+            bases = np.frombuffer(source, np.uint8) if isinstance(source, (bytes, bytearray, memoryview)) else \
+                np.ascontiguousarray(source, np.uint8)
+            _check(self.L.mmt_merged_sequences_host(self.engine.h, self.h, _p(bases) if len(bases) else None, len(bases), col, d,
+                                                    term, C.byref(k)))
+        return int(k.value)
+
+    def sequences_offsets(self):
+        """uint64 [n_rows + 1]: record i of the last sequences() is bytes [offsets[i], offsets[i + 1]) of the text"""
+        out = np.zeros(self.n_rows + 1, np.uint64)
+        _check(self.L.mmt_merged_sequences_offsets(self.h, _p(out)))
+        return out
+
+    def sequences_offsets_device(self):
+        """address of the u64 [n_rows + 1] record offsets in HBM"""
+        a = C.c_void_p()
+        _check(self.L.mmt_merged_sequences_offsets_device(self.h, C.byref(a)))
+        return a.value or 0
+
+    def sequences_text(self):
+        """the multi-FASTA of the last sequences(), formatted on the device"""
+        k = C.c_size_t()
+        ptr = self.L.mmt_merged_sequences_text(self.h, C.byref(k))
+        if not ptr:
+            raise MumemtoError("libmumemto: %s" % self.L.mmt_last_error().decode(errors="replace"))
+        return _bytes_at(ptr, k.value)
+
+    def write_sequences(self, path):
+        _check(self.L.mmt_merged_sequences_write_text(self.h, os.fsencode(path)))
+
+    def sequences_stats(self):
+        st = (C.c_double * 8)()
+        _check(self.L.mmt_merged_sequences_stats(self.h, st))
+        d = dict(measure_ms=float(st[0]), format_ms=float(st[1]))
+        d.update(records=int(st[2]), bases=int(st[3]), clipped=int(st[4]), empty=int(st[5]), text_bytes=int(st[6]),
+                 pieces=int(st[7]))
+        return d
+
     def text(self):
         k = C.c_size_t()
         ptr = self.L.mmt_merged_text(self.h, C.byref(k))
@@ -1176,6 +1248,29 @@ class Merged:
 
     def write_text(self, path):
         _check(self.L.mmt_merged_write_text(self.h, os.fsencode(path)))
+
+
+SEQ_DIALECTS = {"binary": 0, "python": 1}
+
+
+def _engine_text_packed(self):
+    """the layout of the resident text: True = two bits per base, False = a byte per base, None = no text is held"""
+    r = self.L.mmt_engine_text_packed(self.h)
+    return None if r < 0 else bool(r)
+
+
+Engine.text_packed = _engine_text_packed
+
+
+def _engine_mum_sequences(self, col, dialect="python", terminator=True):
+    """the multi-FASTA of the MUM rows of this engine's last run in document col, read from the rows and the text where they
+    lie in HBM (Merged.sequences with the resident source)"""
+    with Merged.from_device(self, *self.rows_mum_device()) as m:
+        m.sequences(col, None, dialect, terminator)
+        return m.sequences_text()
+
+
+Engine.mum_sequences = _engine_mum_sequences
 
 
 def collinear_blocks(lengths, starts, strands, max_break=1000, min_singleton_length=None, device=0):
@@ -1367,6 +1462,20 @@ def get_sequence_info(lengths, starts, strands, contigs, blocks=None, names=Fals
                 m.set_blocks(blocks)
             m.label(contigs, names)
             return m.label_cells() + (m.label_text(),)
+    finally:
+        eng.close()
+
+
+def extract_mums(lengths, starts, strands, source, col=0, dialect="python", terminator=True, path=None, device=0):
+    """Rows on the host and the bases of document col (bytes, a uint8 array or a FASTA path) -> the multi-FASTA of the rows'
+    sequences as bytes, or with path written to that file (and None returned); dialects as in Merged.sequences"""
+    eng = Engine(device)
+    try:
+        with Merged.from_rows(eng, lengths, starts, strands) as m:
+            m.sequences(col, source, dialect, terminator)
+            if path is None:
+                return m.sequences_text()
+            m.write_sequences(path)
     finally:
         eng.close()
 

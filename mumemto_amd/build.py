@@ -20,7 +20,7 @@ ARCH = "gfx950"
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-result",
             "--offload-arch=" + ARCH]
 
-LIB_SOURCES = ["kernels.hip", "prims.hip", "parse_lcp.hip", "pfp_kernels.hip", "rows_kernels.hip", "merge_kernels.hip", "digest_kernels.hip", "engine.cpp", "sorter.cpp", "pfp.cpp", "guided.cpp", "guided_kernels.hip", "pool.cpp", "dist.cpp", "merge.cpp", "collinear.cpp", "collinear_kernels.hip", "inversion.cpp", "inversion_kernels.hip", "coverage.cpp", "coverage_kernels.hip", "density.cpp", "density_kernels.hip", "bed.cpp", "bed_kernels.hip", "label.cpp", "label_kernels.hip", "string_fold.cpp", "string_fold_kernels.hip", "piece_writer.cpp", "text_pieces.cpp", "contig_table.cpp", "partitioned.cpp", "api.cpp",
+LIB_SOURCES = ["kernels.hip", "prims.hip", "parse_lcp.hip", "pfp_kernels.hip", "rows_kernels.hip", "merge_kernels.hip", "digest_kernels.hip", "engine.cpp", "sorter.cpp", "pfp.cpp", "guided.cpp", "guided_kernels.hip", "pool.cpp", "dist.cpp", "merge.cpp", "collinear.cpp", "collinear_kernels.hip", "inversion.cpp", "inversion_kernels.hip", "coverage.cpp", "coverage_kernels.hip", "density.cpp", "density_kernels.hip", "bed.cpp", "bed_kernels.hip", "label.cpp", "label_kernels.hip", "sequences.cpp", "sequence_kernels.hip", "string_fold.cpp", "string_fold_kernels.hip", "piece_writer.cpp", "text_pieces.cpp", "contig_table.cpp", "partitioned.cpp", "api.cpp",
                "cxx_api.cpp", "fasta.cpp", "base_pack.cpp", "options.cpp"]
 TOOLS = {"mumemto_exec": ["cli_main.cpp"], "anchor_merge": ["merge_main.cpp"]}
 HOST_TOOLS = {"extract_mums": ["extract_mums_main.cpp", "fasta.cpp"]}     # no device code: plain g++

@@ -23,6 +23,7 @@
 #include "collinear.hpp"
 #include "bed.hpp"
 #include "label.hpp"
+#include "sequences.hpp"
 #include "string_fold.hpp"
 #include "coverage.hpp"
 #include "density.hpp"
@@ -117,6 +118,8 @@ struct mmt_merged {
     mmt::LabelStats label;             // of the last mmt_merged_label, and of the text written since
     std::string label_text;            // of the last mmt_merged_label_text
     mmt::StringFoldStats sfold;        // of the mmt_string_fold that made the rows
+    mmt::SequencesStats seq;           // of the last mmt_merged_sequences*, and of the text written since
+    std::string seq_text;              // of the last mmt_merged_sequences_text
 };
 
 extern "C" {
@@ -496,6 +499,7 @@ int mmt_column_bytes(const mmt_engine* e, uint32_t out[3]) {
 }
 int mmt_copy_sa64(const mmt_engine* e, uint64_t* out) { if (!e) return fail(1, "null"); MMT_TRY e->e->copy_sa64(out); MMT_CATCH }
 int mmt_is_wide(const mmt_engine* e) { return e && e->e->wide() ? 1 : 0; }
+int mmt_engine_text_packed(const mmt_engine* e) { return !e || !e->e->have_text() ? -1 : e->e->packed_text() ? 1 : 0; }
 size_t mmt_scan_ranges(const mmt_engine* e) { return e ? e->e->scan_ranges() : 0; }
 int mmt_engine_set_stream_host40(mmt_engine* e, const uint32_t* sa_lo, const uint8_t* sa_hi, const uint32_t* lcp,
                                  const uint8_t* bwt, uint64_t entries, const uint64_t* doc_len, size_t n_docs,
@@ -1048,6 +1052,73 @@ int mmt_merged_label_stats(const mmt_merged* m, double out[8]) {
     for (int i = 0; i < 4; i++) out[i] = S.ms[i];
     out[4] = (double)(has ? S.cells : 0); out[5] = (double)(has ? S.absent : 0); out[6] = (double)(has ? S.hbm_columns : 0);
     out[7] = (double)(has ? S.text_bytes : 0);
+    return 0;
+}
+// ---- multi-MUM sequences (sequences.cpp) -----------------------------------------------------
+namespace {
+int merged_sequences(mmt_engine* e, mmt_merged* m, const mmt::SeqSource& source, const char* fasta, int64_t col, int dialect,
+                     int terminator, uint64_t* doc_len, uint64_t* text_bytes) {
+    if (!e || !m) return fail(1, "engine and merged rows must be non-null");
+    if (e->e.get() != m->engine) return fail(1, "the merged rows belong to another engine");
+    MMT_TRY
+    m->seq_text.clear();
+    if (fasta) mmt::sequences_file(*e->e, m->rows, fasta, col, (mmt::SeqDialect)dialect, terminator != 0, &m->seq, doc_len);
+    else mmt::sequences(*e->e, m->rows, source, col, (mmt::SeqDialect)dialect, terminator != 0, &m->seq);
+    if (text_bytes) *text_bytes = m->seq.text_bytes;
+    MMT_CATCH
+}
+}  // namespace
+int mmt_merged_sequences(mmt_engine* e, mmt_merged* m, int64_t col, int dialect, int terminator, uint64_t* text_bytes) {
+    return merged_sequences(e, m, mmt::SeqSource(), nullptr, col, dialect, terminator, nullptr, text_bytes);
+}
+int mmt_merged_sequences_host(mmt_engine* e, mmt_merged* m, const uint8_t* bases, uint64_t n_bases, int64_t col, int dialect,
+                              int terminator, uint64_t* text_bytes) {
+    mmt::SeqSource source;
+    source.resident = false; source.bases = bases; source.n = n_bases;
+    return merged_sequences(e, m, source, nullptr, col, dialect, terminator, nullptr, text_bytes);
+}
+int mmt_merged_sequences_file(mmt_engine* e, mmt_merged* m, const char* fasta_path, int64_t col, int dialect, int terminator,
+                              uint64_t* n_bases, uint64_t* text_bytes) {
+    if (!fasta_path) return fail(1, "null");
+    return merged_sequences(e, m, mmt::SeqSource(), fasta_path, col, dialect, terminator, n_bases, text_bytes);
+}
+int mmt_merged_sequences_offsets(const mmt_merged* m, uint64_t* offsets) {
+    if (!m || !offsets) return fail(1, "null");
+    if (!m->rows.has_sequences) return fail(3, "no sequences attached: call mmt_merged_sequences first");
+    MMT_TRY
+    hipStream_t st = m->engine->stream();
+    MMT_HIP(hipSetDevice(m->engine->device()));
+    MMT_HIP(hipMemcpyAsync(offsets, m->rows.d_seq_offset.get(), (m->rows.n_rows + 1) * 8, hipMemcpyDeviceToHost, st));
+    MMT_HIP(hipStreamSynchronize(st));
+    MMT_CATCH
+}
+int mmt_merged_sequences_offsets_device(const mmt_merged* m, const uint64_t** offsets) {
+    if (!m || !offsets) return fail(1, "null");
+    if (!m->rows.has_sequences) return fail(3, "no sequences attached: call mmt_merged_sequences first");
+    *offsets = m->rows.d_seq_offset.get();
+    return 0;
+}
+const char* mmt_merged_sequences_text(mmt_merged* m, size_t* len) {
+    if (len) *len = 0;
+    if (!m) { fail(1, "null"); return nullptr; }
+    try { m->seq_text = mmt::sequences_text(*m->engine, m->rows, &m->seq); }
+    catch (const std::exception& ex) { fail(3, ex.what()); return nullptr; }
+    if (len) *len = m->seq_text.size();
+    return m->seq_text.data();
+}
+int mmt_merged_sequences_write_text(mmt_merged* m, const char* path) {
+    if (!m || !path) return fail(1, "null");
+    MMT_TRY
+    mmt::sequences_write_text(*m->engine, m->rows, path, &m->seq);
+    MMT_CATCH
+}
+int mmt_merged_sequences_stats(const mmt_merged* m, double out[8]) {
+    if (!m || !out) return fail(1, "null");
+    const mmt::SequencesStats& S = m->seq;
+    const bool has = m->rows.has_sequences;
+    out[0] = S.ms[0]; out[1] = S.ms[1];
+    out[2] = (double)(has ? S.records : 0); out[3] = (double)(has ? S.bases : 0); out[4] = (double)(has ? S.clipped : 0);
+    out[5] = (double)(has ? S.empty : 0); out[6] = (double)(has ? S.text_bytes : 0); out[7] = (double)S.pieces;
     return 0;
 }
 // ---- string-based merge, last step (string_fold.cpp) -------------------------------------------

@@ -116,6 +116,7 @@ struct PinnedBytes {
 
 // document layout of the text: starts of the documents, total length, device copy of the starts
 void Engine::layout_docs(bool revcomp) {
+    text_generation_++;
     const size_t N = doc_len_.size();
     revcomp_ = revcomp;
     doc_start_.assign(N + 1, 0);

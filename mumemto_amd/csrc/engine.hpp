@@ -250,6 +250,10 @@ public:
     uint64_t text_length() const { return n_; }
     size_t n_docs() const { return doc_len_.size(); }
     const std::vector<uint64_t>& doc_len() const { return doc_len_; }
+    // text position of the first base of document d's forward strand (n_docs + 1 entries; sequences.cpp)
+    const std::vector<uint64_t>& doc_start() const { return doc_start_; }
+    // counts the texts this engine has laid out: a reading of the resident text kept elsewhere (sequences.cpp) is stale once it moves on
+    uint64_t text_generation() const { return text_generation_; }
     hipStream_t stream() const { return stream_; }
     int device() const { return device_; }
 
@@ -356,7 +360,7 @@ private:
     std::vector<uint64_t> doc_len_, doc_base_, doc_start_;
     DevBuf<uint64_t> d_doc_base_, d_doc_start_;
     bool revcomp_ = true;
-    uint64_t n_ = 0;
+    uint64_t n_ = 0, text_generation_ = 0;
     bool wide_ = false;                   // this text runs with 40-bit positions (wide.hpp)
     bool input_valid_ = false;
     bool drop_input_after_text_ = false;  // host-fed runs upload the bases for every run: they are dead once T exists

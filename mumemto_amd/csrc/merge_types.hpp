@@ -56,19 +56,29 @@ struct MergedRows {
     bool has_string_thresh = false;
     size_t string_thresh_len = 0;
     DevBuf<uint16_t> d_string_thresh, d_string_thresh_rev;
+    // multi-MUM sequences (sequences.hpp), attached by sequences(): a reading of one column of the table and of a text; whatever
+    // replaces the table drops them
+    bool has_sequences = false, seq_resident = false, seq_terminator = true;
+    int seq_dialect = 0;
+    uint64_t seq_text_len = 0, seq_bytes = 0;      // length of the text the sources point into; bytes of all records
+    uint64_t seq_text_generation = 0;              // resident: Engine::text_generation() when the records were measured
+    DevBuf<uint64_t> d_seq_offset;                 // n_rows + 1: where every record begins
+    DevBuf<uint64_t> d_seq_source;                 // n_rows: text position of the record's first forward base (bit 63: reverse)
+    DevBuf<uint32_t> d_seq_bases;                  // n_rows: bases written
+    DevBuf<uint8_t> d_seq_text;                    // a document handed over, one byte per base in TextRef's byte layout
 
     MergedRows() = default;
     MergedRows(MergedRows&&) noexcept = default;
     MergedRows& operator=(MergedRows&&) noexcept = default;
 
     // Which results go when something they read is replaced -- the one place that says so.  Blocks, calls and BED records are
-    // row ranges and readings of the blocks; coverage and labels read the table alone.  (A tool clears its OWN flag on entry.)
+    // row ranges and readings of the blocks; coverage, labels and sequences read the table alone.  (A tool clears its OWN flag on entry.)
     // new blocks (collinear_blocks, set_blocks): calls and BED records go, coverage and labels stay
     void blocks_replaced() { has_calls = false; n_calls = 0; has_bed = false; }
     // a new table or row order (sort_like_direct, collinear_blocks): everything attached goes
     void table_replaced() {
         has_blocks = false; n_blocks = 0; blocks_replaced(); has_coverage = false; has_label = false;
-        has_string_thresh = false; string_thresh_len = 0;
+        has_string_thresh = false; string_thresh_len = 0; has_sequences = false;
     }
 };
 

@@ -5,7 +5,8 @@ Host-side twin of the reference's merge driver (mumemto/merge_mums.py; command l
 
 * every PREFIX.athresh present  -> anchor-based merge: `anchor_merge` (GPU fold, csrc/merge.cpp);
 * every PREFIX.thresh present   -> string-based merge:
-    1. `extract_mums` writes each partition's MUM strings as a multi-FASTA, one `#`-terminated record per row;
+    1. `extract_mums` writes each partition's MUM strings as a multi-FASTA, one `#`-terminated record per row; with
+       `--extract-on-device` (an addition) the library does, on the GPU (csrc/sequences.cpp, the binary's bytes);
     2. `mumemto_exec` (the GPU hot path) finds the multi-MUMs of those collections ("MUMs of MUMs");
     3. `string_merge` below maps every such match back through the partitions' rows and thresholds; with `--device`
        (an addition) the library's string fold does, in HBM (csrc/string_fold.cpp, held to `string_merge` byte for byte).
@@ -40,6 +41,8 @@ def parse_arguments(argv=None):
     ap.add_argument("--verbose", "-v", action="store_true", help="Print verbose output")
     ap.add_argument("--device", action="store_true",
                     help="Run the last step of a string merge (rows and thresholds) on the GPU as well (MUMEMTO_DEVICE chooses it)")
+    ap.add_argument("--extract-on-device", dest="extract_on_device", action="store_true",
+                    help="Write the MUM strings of a string merge (step 1) on the GPU instead of running extract_mums")
     args = ap.parse_args(argv)
     if len(args.mum_files) < 2:
         ap.error("At least two MUMs files are required for merging")
@@ -230,10 +233,32 @@ def _tool(name):
     return path
 
 
+def extract_on_device(mum_file, prefix):
+    """step 1 through the library (csrc/sequences.cpp): PREFIX_mums.fa with the bytes the extract_mums binary writes -- the rows
+    of the file in its order, the first document of PREFIX.lengths, every record `#`-terminated -- by the package's own
+    extract_mums tool, in a process of its own like the binary.  -> 0, or 1 where the merge cannot go on.  Like the binary, a
+    row without a start in ANY document stops it (the device tool alone would refuse only one without a start in the first).
+    Unlike the binary, the tool also stops when the first document's length is not the one PREFIX.lengths states, or when
+    the table and PREFIX.lengths differ in their number of sequences; the binary does not look at either."""
+    try:
+        if (mumsio.read_rows(mum_file)[1] < 0).any():
+            print("Error: %s holds partial multi-MUMs (a row without a start in some document)" % mum_file, file=sys.stderr)
+            return 1
+    except (OSError, ValueError, IndexError) as ex:
+        print("Error: %s" % ex, file=sys.stderr)
+        return 1
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([root] + [p for p in [os.environ.get("PYTHONPATH")] if p]))
+    cmd = [sys.executable, "-m", "mumemto_amd.extract_mums", "--dialect", "binary", "-m", mum_file, "-f", prefix + ".lengths",
+           "-i", "0", "-o", prefix + "_mums.fa", "--device", os.environ.get("MUMEMTO_DEVICE", "0")]
+    return subprocess.run(cmd, env=env).returncode
+
+
 def run_merger(args):
     """extract the MUM strings of every partition and find their multi-MUMs on the GPU (merge_mums.py:138-168)"""
-    for f in args.mum_files:
-        if subprocess.run([_tool("extract_mums"), "-m", f]).returncode != 0:
+    for f, p in zip(args.mum_files, args.paths):
+        rc = extract_on_device(f, p) if args.extract_on_device else subprocess.run([_tool("extract_mums"), "-m", f]).returncode
+        if rc != 0:
             print("Error: Partial MUMs detected. Aborting merge. Cleaning up...", file=sys.stderr)
             for p in args.paths:
                 if os.path.exists(p + "_mums.fa"):
